@@ -2567,6 +2567,9 @@ struct GpuOp {
                                          ring's wrap memset would race the
                                          other stream's running merge) */
     uint64_t fire_seq, fire_seq2;
+    /* row cursor of the latest fire into d_out ([0]) / d_out2 ([1]); read
+     * back only by arroyo_amd_last_emission */
+    unsigned long long *last_cur[2];
     int64_t out_rows_cap;
 
     /* host-accumulated emission (emit_to_host) */
@@ -3661,6 +3664,7 @@ static int fire_window(GpuOp *o, const std::vector<uint32_t> &src,
             cur = o->d_fire_cur + (o->fire_seq & 63);
             o->fire_seq++;
         }
+        o->last_cur[on_f2] = cur;
         if (!src.empty()) {
             MergeFusedArgs M = {};
             M.ring = o->ring;
@@ -3816,6 +3820,8 @@ static int fire_window(GpuOp *o, const std::vector<uint32_t> &src,
             C.out[i] = o->d_out[i];
     }
     C.n_out = o->d_n_out;
+    /* a raw-state drain overwrites d_out: no window emission left there */
+    o->last_cur[0] = raw_states ? nullptr : o->d_n_out;
     int blocks = (int)((o->CM + 255) / 256);
     if (blocks > 1024) blocks = 1024;   /* 1 global cursor atomic per block */
     hipLaunchKernelGGL(k_compact, dim3(blocks), dim3(256), 0, o->stream, C);
@@ -3880,6 +3886,7 @@ static int fire_dual(GpuOp *o, const GpuOp::PendFire &A,
     unsigned long long *cur = o->d_fire_cur + (o->fire_seq & 63);
     o->fire_seq++;
     o->fire_alt++;
+    o->last_cur[0] = cur;
     MergeDualArgs M = {};
     M.ring = o->ring;
     std::vector<uint32_t> uni = A.src;
@@ -4547,6 +4554,40 @@ API int arroyo_amd_perf(void *h, double *update_ms, int64_t *rows,
     o->launches = 0;
     o->emitted_device_rows = 0;
     return 0;
+}
+
+/* output introspection for bench.py's --dump-outputs: host copy of the
+ * window emissions still resident in the device output buffers -- the
+ * latest fire into d_out and, with two fire streams, into d_out2.  Read
+ * only; the device-resident path itself never copies these out. */
+API int arroyo_amd_last_emission(void *h, AmdOutBatch *out) {
+    GpuOp *o = (GpuOp *)h;
+    if (arroyo_amd_sync(h)) return 1;
+    std::vector<std::vector<int64_t>> rows(o->out_cols);
+    for (int b = 0; b < 2; b++) {
+        if (!o->last_cur[b]) continue;
+        int64_t *const *outv = b ? o->d_out2 : o->d_out;
+        unsigned long long n = 0;
+        HIP_CHECK(o, hipMemcpy(&n, o->last_cur[b], 8, hipMemcpyDeviceToHost));
+        if ((int64_t)n > o->out_rows_cap) {
+            snprintf(o->err_msg, sizeof o->err_msg,
+                     "last_emission: row cursor %llu exceeds the output "
+                     "buffer (%lld rows)", n, (long long)o->out_rows_cap);
+            return 1;
+        }
+        if (n == 0) continue;
+        for (int i = 0; i < o->out_cols; i++) {
+            size_t old = rows[i].size();
+            rows[i].resize(old + n);
+            HIP_CHECK(o, hipMemcpy(rows[i].data() + old, outv[i], n * 8,
+                                   hipMemcpyDeviceToHost));
+        }
+    }
+    /* build_out packs (and clears) host_out: lend it these rows */
+    rows.swap(o->host_out);
+    int rc = build_out(o, out, 0);
+    rows.swap(o->host_out);
+    return rc;
 }
 
 /* streaming-read bandwidth calibration (debug/measurement only) */

@@ -10,7 +10,7 @@ import subprocess
 
 import numpy as np
 
-from arroyo_amd.cabi import WindowOp
+from arroyo_amd.cabi import AmdOutBatch, WindowOp, _out_to_numpy
 
 _DIR = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_DIR, "libarroyo_amd.so")
@@ -70,6 +70,9 @@ def lib():
             ctypes.c_void_p, ctypes.c_uint64]
         _lib.arroyo_amd_mark_epoch.restype = ctypes.c_int
         _lib.arroyo_amd_mark_epoch.argtypes = [ctypes.c_void_p]
+        _lib.arroyo_amd_last_emission.restype = ctypes.c_int
+        _lib.arroyo_amd_last_emission.argtypes = [
+            ctypes.c_void_p, ctypes.POINTER(AmdOutBatch)]
         _lib.arroyo_amd_partition.restype = ctypes.c_int
         _lib.arroyo_amd_partition.argtypes = [ctypes.c_void_p] * 3 + [
             ctypes.c_int64, ctypes.c_uint32] + [ctypes.c_void_p] * 3 + [
@@ -111,6 +114,18 @@ class GpuWindowOp(WindowOp):
             watermark if watermark is not None else 0)
         if rc != 0:
             raise RuntimeError(self._fn["last_error"](self._h).decode())
+
+    def last_emission(self):
+        """Host copy of the window emissions still resident in the device
+        output buffers (the latest fired window per fire stream), as numpy
+        columns [key?, aggs..., window_start, window_end, _timestamp]."""
+        out = AmdOutBatch()
+        rc = lib().arroyo_amd_last_emission(self._h, ctypes.byref(out))
+        if rc != 0:
+            raise RuntimeError(self._fn["last_error"](self._h).decode())
+        cols = _out_to_numpy(out)
+        self._fn["free_out"](ctypes.byref(out))
+        return cols
 
     def perf(self):
         ms = ctypes.c_double()

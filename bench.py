@@ -18,7 +18,15 @@ Workload = BASELINE.json configs[1]: q5 hot-items, 10s width / 2s slide
 COUNT GROUP BY auction, 64K-row batches (configs[0] is the reference's
 CPU-runnable plumbing case; the others are parity-test cases).
 
-Usage: python bench.py --gpus N --steps K --warmup W
+Usage: python bench.py --gpus N --steps K --warmup W [--full]
+                       [--dump-outputs DIR]
+A plain run sets up, warms up, times exactly K steps and prints the result
+line.  --full adds the legs that take runs of their own (cpu_baseline,
+boundary_host); without it those fields are null.  --dump-outputs writes
+what the last timed step left for the next pipeline stage -- the newest
+fired windows, read back from the device output buffers after the timed
+region, and the emitted-row count -- as DIR/<name>.npy (float64, sorted
+rows; inputs are seeded, so two builds can be compared file for file).
 For N>1 the driver launches this under torch.distributed.run, one rank per
 GPU; each rank processes its own 64K-row batch per step and the keyed
 shuffle (device partition kernel + RCCL all-to-all over xGMI) runs inside
@@ -29,9 +37,10 @@ Emits ONE JSON line from rank 0, including:
     HIP-event launch time, measured on the operator's own stream) vs the
     8 TB/s HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md);
     algorithmic bytes = 16 B/row (key i64 + _timestamp i64), see DESIGN.md.
-  - cpu_baseline: the CPU oracle (oracle/arroyo_oracle.c, a restatement of
-    the reference's operator — kind "port") timed on this box's host cores
-    over a bounded sample of the same workload, rank 0 at N=1 only.
+  - cpu_baseline (--full only): the CPU oracle (oracle/arroyo_oracle.c, a
+    restatement of the reference's operator — kind "port") timed on the
+    host's cores over a bounded sample of the same workload, rank 0 at N=1
+    only.
 """
 import argparse
 import ctypes
@@ -65,9 +74,8 @@ HBM_PEAK_GBPS = 8000.0           # spec peak (MI355X_MICROARCH.md)
 ALG_BYTES_PER_ROW = 16           # compulsory HBM read: auction i64 + ts i64
 CPU_SAMPLE_ROWS = 64_000_000
 HOST_SAMPLE_ROWS = 32_000_000    # host-pointer boundary leg sample
-# the timed region must cover at least this much wall time regardless of
-# --steps, so a short driver invocation cannot overstate steady-state rate
-MIN_TIMED_S = float(os.environ.get("BENCH_MIN_TIMED_S", "0.25"))
+DUMP_MAX_BYTES = 48 << 20        # --dump-outputs budget (hard limit 64 MB)
+DUMP_SAMPLE_SEED = 1234
 
 
 def op_config(device):
@@ -344,7 +352,6 @@ def run_gpu(args):
 
     clock = WatermarkClock()
     torch.cuda.synchronize()
-    tw0 = time.perf_counter()
     step_exchange = os.environ.get("BENCH_STEP_EXCHANGE") == "1"
     if world == 1:
         run_span(0, args.warmup)
@@ -354,57 +361,50 @@ def run_gpu(args):
     else:
         run_span_dist(0, args.warmup)
     torch.cuda.synchronize()
-    tw1 = time.perf_counter()
     op.perf()  # reset kernel-time counters after warmup
 
-    # enforce a minimum timed duration regardless of --steps: run the
-    # requested step count, then keep extending (doubling) the timed
-    # region until it covers >= MIN_TIMED_S of wall time.  All ranks agree
-    # on each extension (max-elapsed all-reduce before the decision), so
-    # the per-step collectives stay in lockstep.
-    del tw0, tw1
+    # the timed region is exactly --steps steps; with N>1 every rank
+    # reports the slowest rank's time (max all-reduce)
     wm_fires[0] = 0
-    elapsed = 0.0
-    timed_steps = 0
-    chunk = args.steps
-    s_cursor = args.warmup
-    while True:
-        if dist:
-            dist.barrier()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        if world == 1:
-            run_span(s_cursor, chunk)
-        elif step_exchange:
-            for s in range(s_cursor, s_cursor + chunk):
-                one_step(s)
-        else:
-            run_span_dist(s_cursor, chunk)
-        torch.cuda.synchronize()
-        if dist:
-            dist.barrier()
-        t1 = time.perf_counter()
-        s_cursor += chunk
-        timed_steps += chunk
-        elapsed += t1 - t0
-        e_all = elapsed
-        if dist:
-            e = torch.tensor([elapsed], device=dev)
-            dist.all_reduce(e, op=dist.ReduceOp.MAX)
-            e_all = float(e.item())
-        if e_all >= MIN_TIMED_S:
-            elapsed = e_all
-            break
-        chunk = max(chunk, timed_steps)   # double the region each pass
+    timed_steps = args.steps
+    if dist:
+        dist.barrier()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    if world == 1:
+        run_span(args.warmup, timed_steps)
+    elif step_exchange:
+        for s in range(args.warmup, args.warmup + timed_steps):
+            one_step(s)
+    else:
+        run_span_dist(args.warmup, timed_steps)
+    torch.cuda.synchronize()
+    if dist:
+        dist.barrier()
+    t1 = time.perf_counter()
+    elapsed = t1 - t0
+    if dist:
+        e = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+        dist.all_reduce(e, op=dist.ReduceOp.MAX)
+        elapsed = float(e.item())
 
     if world == 1:
         drain_pending()
     perf = op.perf()
     perf["wm_fires_timed"] = wm_fires[0]
+    outputs = None
+    if args.dump_outputs:
+        # what the next pipeline stage would find after the last timed step:
+        # the newest fired windows, still resident in the operator's device
+        # output buffers, and the running emitted-row count
+        outputs = {
+            "last_windows": op.last_emission(),
+            "emitted_rows": perf["emitted_device_rows"],
+        }
     op.close()
     if dist:
         dist.destroy_process_group()
-    return elapsed, perf, rank, world, timed_steps
+    return elapsed, perf, rank, world, timed_steps, outputs
 
 
 def _oracle_run(key, ts):
@@ -535,20 +535,63 @@ def host_boundary_leg():
     }
 
 
+def dump_outputs(outdir, outputs, rank, world):
+    """Write the last timed step's outputs as <name>.npy (float64: keys and
+    counts are integers below 2^53 and the window bounds whole seconds in
+    ns, multiples of 2^9, so the conversion from int64 is exact).  Rows
+    of a fired window leave the kernel in no fixed order, so they are sorted
+    first; an emission over the size budget is cut to a fixed seeded sample
+    of its sorted rows, the same rows on every run."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    suffix = "" if world == 1 else f"_rank{rank}"
+    cols = outputs["last_windows"]
+    rows = (np.stack(cols, axis=1) if cols
+            else np.empty((0, 0), dtype=np.int64))
+    if rows.shape[0]:
+        # total order over [key, count, window_start, window_end,
+        # _timestamp], key major
+        rows = rows[np.lexsort(tuple(rows[:, ::-1].T))]
+        max_rows = DUMP_MAX_BYTES // (8 * rows.shape[1])
+        if rows.shape[0] > max_rows:
+            rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+            pick = np.sort(rng.choice(rows.shape[0], size=max_rows,
+                                      replace=False))
+            rows = rows[pick]
+    np.save(os.path.join(outdir, f"last_windows{suffix}.npy"),
+            rows.astype(np.float64))
+    np.save(os.path.join(outdir, f"emitted_rows{suffix}.npy"),
+            np.array([outputs["emitted_rows"]], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=400)
+    ap.add_argument("--steps", type=int, default=400,
+                    help="number of timed steps (exactly)")
     ap.add_argument("--warmup", type=int, default=100)
-    ap.add_argument("--skip-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run, also time the CPU oracle "
+                         "baseline and the host-pointer boundary leg "
+                         "(N=1 only)")
+    ap.add_argument("--skip-cpu-baseline", action="store_true",
+                    help="with --full: skip those legs after all")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left for the next "
+                         "stage as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     if args.gpus > 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         raise SystemExit(
             "--gpus N>1 must run under torch.distributed.run with "
             "--nproc-per-node N (one rank per GPU); a single-process run "
             "would misreport whole-job throughput")
-    elapsed, perf, rank, world, timed_steps = run_gpu(args)
+    elapsed, perf, rank, world, timed_steps, outputs = run_gpu(args)
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs, rank, world)
     if rank != 0:
         return
 
@@ -564,7 +607,7 @@ def main():
 
     cpu = None
     boundary = None
-    if world == 1 and not args.skip_cpu_baseline:
+    if args.full and world == 1 and not args.skip_cpu_baseline:
         cpu = cpu_baseline()
         boundary = host_boundary_leg()
 

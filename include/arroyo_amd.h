@@ -133,6 +133,12 @@ const char *arroyo_amd_last_error(void *h);
 int arroyo_amd_perf(void *h, double *update_ms, int64_t *rows,
                     int64_t *launches, int64_t *emitted_device_rows);
 
+/* Output introspection for the measurement harness: host copy of the window
+ * emissions still resident in the device output buffers (the latest fired
+ * window per fire stream; row order within a window is unspecified).  Free
+ * with arroyo_amd_free_out. */
+int arroyo_amd_last_emission(void *h, AmdOutBatch *out);
+
 /* Device-side key-hash partitioning (shuffle): writes rows regrouped into
  * per-partition contiguous segments and per-partition counts. */
 int arroyo_amd_partition(const int64_t *d_keys, const int64_t *d_vals,

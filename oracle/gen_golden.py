@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
-"""Generate golden parity fixtures under tests/golden/ from the reference
-checkout at /root/reference (ArroyoSystems/arroyo).
+"""Generate golden parity fixtures under tests/golden/ from a checkout of
+the reference (ArroyoSystems/arroyo): GOLDEN_REF names its
+crates/arroyo-sql-testing directory, or any directory with the same
+inputs/ + golden_outputs/ layout.
 
-Run in the build container (where /root/reference is mounted); the committed
-outputs travel to GPU boxes where the reference does not exist.  The fixtures
+The committed outputs travel wherever the tests run; the reference itself is
+not needed there (tests/golden/raw/inputs/ keeps the three raw input files
+this script reads, xz-compressed, so the extraction can be re-run from the
+repository alone, see tests/test_oracle_golden.py).  The fixtures
 are the reference's own end-to-end test vectors for the windowed-aggregate
 operator (crates/arroyo-sql-testing: inputs/ + golden_outputs/), re-encoded as
 columnar JSON with integer nanosecond timestamps (the wire shape our C-ABI
@@ -23,7 +27,7 @@ import json
 import os
 from datetime import datetime as dt, timezone
 
-REF = "/root/reference/crates/arroyo-sql-testing"
+REF = os.environ.get("GOLDEN_REF")
 OUT = os.environ.get(
     "GOLDEN_OUT",
     os.path.join(os.path.dirname(__file__), "..", "tests", "golden"))
@@ -46,6 +50,9 @@ def load_rows(path):
 
 
 def main():
+    if not REF or not os.path.isdir(REF):
+        raise SystemExit("set GOLDEN_REF to the reference's "
+                         "crates/arroyo-sql-testing directory")
     os.makedirs(OUT, exist_ok=True)
 
     impulse = load_rows(f"{REF}/inputs/impulse.json")

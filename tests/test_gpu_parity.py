@@ -442,3 +442,36 @@ def test_dual_window_merge_matches_sequential(monkeypatch):
     a.close()
     b.close()
     assert_parity(concat_outputs(outs[0]), concat_outputs(outs[1]))
+
+
+def test_last_emission_reads_back_newest_windows():
+    """arroyo_amd_last_emission (bench.py --dump-outputs) copies out what a
+    device-resident operator (emit_to_host=False) left in its output
+    buffers: the newest fired window per fire stream.  Those rows must be
+    exactly what a host-emitting operator returned for the same windows."""
+    cols = nexmark.bids(500_000, events_per_sec=50_000, seed=41)
+    kw = dict(width_ns=10 * NS, slide_ns=2 * NS, n_keys=1, n_value_cols=0,
+              aggs=[(cabi.COUNT, -1)], log2_capacity=16)
+    host = gpu_op(**kw)
+    dev = gpu_op(emit_to_host=False, **kw)
+    assert all(len(c) == 0 for c in dev.last_emission())   # nothing fired
+    outs = []
+    for cb in batches_from_columns(cols, 40_000):
+        host.process_batch(cb)
+        dev.process_batch(cb)
+        wm = int(cb[-1][-1]) - NS
+        out = host.handle_watermark(wm)
+        if out and len(out[0]):
+            outs.append(out)
+        assert len(dev.handle_watermark(wm)[0]) == 0   # stays on device
+    got = dev.last_emission()
+    host.close()
+    dev.close()
+    want = concat_outputs(outs)
+    ws_col = 2                    # [key, count, window_start, window_end, ts]
+    fired = np.unique(want[ws_col])
+    assert len(fired) >= 3
+    n_bufs = 1 if os.environ.get("ARROYO_AMD_FIRE_STREAM") == "0" else 2
+    assert np.array_equal(np.unique(got[ws_col]), fired[-n_bufs:])
+    newest = np.isin(want[ws_col], fired[-n_bufs:])
+    assert_parity(got, [c[newest] for c in want])

@@ -192,23 +192,43 @@ def test_c_oracle_avg_fuzz(seed):
     cop.close()
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"),
-                    reason="reference checkout absent (GPU box)")
 def test_golden_fixtures_reproducible(tmp_path):
-    """Re-running the extraction against /root/reference must reproduce the
-    committed fixtures bit-for-bit (guards against fixture drift)."""
+    """Re-running the extraction must reproduce the committed fixtures
+    bit-for-bit (guards against fixture drift).  Its source is staged from
+    the repository alone, in the reference's layout: the raw input files
+    (kept xz-compressed under tests/golden/raw/inputs/, from which
+    inputs.json is derived) and the golden outputs, which the fixtures hold row for row
+    and the extraction only re-encodes."""
     import json
+    import lzma
+    import shutil
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, GOLDEN_OUT=str(tmp_path))
+    committed = os.path.join(repo, "tests", "golden")
+    names = sorted(n for n in os.listdir(committed) if n.endswith(".json"))
+    ref, out = tmp_path / "ref", tmp_path / "out"
+    raw = os.path.join(committed, "raw", "inputs")
+    os.makedirs(ref / "inputs")
+    os.makedirs(ref / "golden_outputs")
+    for n in os.listdir(raw):                      # <name>.json.xz
+        with lzma.open(os.path.join(raw, n)) as src, \
+                open(ref / "inputs" / n[:-len(".xz")], "wb") as dst:
+            shutil.copyfileobj(src, dst)
+    suffix = ".golden.json"
+    for n in names:
+        if not n.endswith(suffix):
+            continue
+        with open(os.path.join(committed, n)) as f:
+            rows = json.load(f)
+        with open(ref / "golden_outputs" / (n[:-len(suffix)] + ".json"),
+                  "w") as f:
+            f.writelines(json.dumps(r) + "\n" for r in rows)
+    env = dict(os.environ, GOLDEN_REF=str(ref), GOLDEN_OUT=str(out))
     subprocess.run([sys.executable, os.path.join(repo, "oracle",
                                                  "gen_golden.py")],
                    check=True, env=env, capture_output=True)
-    committed = os.path.join(repo, "tests", "golden")
-    names = sorted(os.listdir(committed))
-    assert names == sorted(os.listdir(tmp_path))
+    assert names == sorted(os.listdir(out))
     for n in names:
-        with open(os.path.join(committed, n)) as f1, \
-                open(tmp_path / n) as f2:
+        with open(os.path.join(committed, n)) as f1, open(out / n) as f2:
             assert json.load(f1) == json.load(f2), n
