@@ -735,6 +735,10 @@ REGR_SYY = 21
 REGR_SXY = 22
 BIT_AND = 23
 BIT_OR = 24
+# order statistics under retraction (updating aggregate only)
+MEDIAN = 25
+MIN_RETRACT = 26
+MAX_RETRACT = 27
 
 
 class AmdUpdatingConfig(ctypes.Structure):

@@ -2836,6 +2836,14 @@ API void *arroyo_amd_create(const AmdWindowConfig *cfg) {
         snprintf(g_err, sizeof g_err, "invalid config");
         return nullptr;
     }
+    for (int i = 0; i < cfg->n_aggs; i++)
+        if (cfg->agg_ops[i] >= AMD_AGG_MEDIAN &&
+            cfg->agg_ops[i] <= AMD_AGG_MAX_RETRACT) {
+            snprintf(g_err, sizeof g_err,
+                     "invalid config: aggregate op %d is updating-aggregate "
+                     "only", cfg->agg_ops[i]);
+            return nullptr;
+        }
     if (!cfg->is_tumbling && cfg->slide_nanos != 0 &&
         cfg->width_nanos % cfg->slide_nanos != 0) {
         /* the reference's planner rejects this (arroyo-planner/src/lib.rs

@@ -1028,6 +1028,14 @@ API void *arroyo_amd_session_create(const AmdSessionConfig *cfg) {
         snprintf(g_sess_err, sizeof g_sess_err, "invalid session config");
         return nullptr;
     }
+    for (int a = 0; a < cfg->n_aggs; a++)
+        if (cfg->agg_ops[a] >= AMD_AGG_MEDIAN &&
+            cfg->agg_ops[a] <= AMD_AGG_MAX_RETRACT) {
+            snprintf(g_sess_err, sizeof g_sess_err,
+                     "invalid session config: aggregate op %d is "
+                     "updating-aggregate only", cfg->agg_ops[a]);
+            return nullptr;
+        }
     int cd_agg = -1;
     for (int a = 0; a < cfg->n_aggs; a++)
         if (cfg->agg_ops[a] == AMD_AGG_COUNT_DISTINCT) {

@@ -16,6 +16,20 @@
  *     split across duplicate chain nodes (two threads can race the first
  *     insert of the same value); the flush walk sums per value, so the
  *     count stays exact without any per-key locking.
+ *   - MEDIAN / MIN_RETRACT / MAX_RETRACT (order statistics under
+ *     retraction) keep the same chained multiset and are evaluated at flush
+ *     by k_updagg_ordstat: one wavefront per changed (key, aggregate)
+ *     gathers the chain's (value, net) nodes once into a per-wave LDS tile
+ *     (or a global scratch arena when the chain is longer than the tile)
+ *     and picks the wanted ranks with an MSB-first weighted radix select
+ *     (up to 8 passes of 8 bits over a 256-bin LDS histogram of net
+ *     counts; leading bytes shared by all of a key's values are skipped).
+ *     Net counts are summed per bucket until the bucket is one value, so a
+ *     value whose refcount is split into +k / -k nodes weighs 0 and is
+ *     never selected.  Known limit, inherited from COUNT DISTINCT: the
+ *     chain is a linked list, so the gather is serial in the chain length;
+ *     cost is linear in the distinct values ever seen per key, because the
+ *     append-only pool never reclaims zero-net nodes.
  *   - Changed-key tracking is a plain per-slot epoch store in the update
  *     kernel (idempotent, no atomics, same cache line as the state);
  *     flush scans the table for the current epoch -- a streaming read at
@@ -49,6 +63,8 @@ namespace updagg {
 #define UERR_POOL_FULL  2
 #define UERR_OUT_CAP    3
 #define UERR_RETRACT    4
+#define UERR_ORD_ROWS   5   /* multiset total != live row count */
+#define UERR_ORD_CHAIN  6   /* chain walk / scratch arena bound hit */
 
 __host__ __device__ inline uint64_t enc_min(int64_t v) {
     return ~(((uint64_t)v) ^ 0x8000000000000000ULL);
@@ -96,7 +112,10 @@ struct UStore {
     uint64_t *st;         /* [(C+1) * SW] scalar states (variable width) */
     int64_t *last;        /* [(C+1) * n_aggs] last emitted values */
     uint32_t *emitted;    /* [C+1] */
-    int32_t *head;        /* [(C+1) * n_aggs] chains (COUNT_DISTINCT) */
+    int32_t *head;        /* [(C+1) * 8] value-multiset chains
+                             (COUNT_DISTINCT, MEDIAN, MIN/MAX_RETRACT) */
+    int64_t *ord;         /* [(C+1) * n_aggs] order-statistic results of the
+                             current flush; null without an ordered agg */
     Node *pool;
     unsigned long long *pool_cur;
     int64_t pool_cap;
@@ -123,7 +142,7 @@ __device__ inline int64_t ukey_slot(const UStore &S, int64_t key, int *err) {
 }
 
 /* add +-1 to value v's net refcount in the (slot, agg) chain.  Fields of a
- * new node are written before the atomicExch publish (release via
+ * new node are written before the atomicCAS publish (release via
  * __threadfence); walkers read them with volatile loads so a stale L1 line
  * covering a freshly-allocated neighbour node is never used. */
 __device__ inline void chain_add(const UStore &S, int64_t slot, int agg,
@@ -142,9 +161,19 @@ __device__ inline void chain_add(const UStore &S, int64_t slot, int agg,
     if (idx >= S.pool_cap) { *err = UERR_POOL_FULL; return; }
     S.pool[idx].value = v;
     S.pool[idx].delta = d;
-    __threadfence();
-    S.pool[idx].next = atomicExch(headp, (int32_t)idx);
-    __threadfence();
+    /* the link is written BEFORE the node becomes reachable (CAS push): a
+     * node published with its `next` still unset would send a concurrent
+     * walker through whatever index the fresh pool memory holds, into some
+     * other (key, aggregate)'s chain, where it could find v and add its
+     * count to the wrong multiset */
+    int32_t old = *(volatile int32_t *)headp;
+    for (;;) {
+        S.pool[idx].next = old;
+        __threadfence();
+        int32_t prev = atomicCAS(headp, old, (int32_t)idx);
+        if (prev == old) break;
+        old = prev;
+    }
 }
 
 struct UpdateArgs {
@@ -215,6 +244,9 @@ k_updagg_update(UpdateArgs A) {
                           (unsigned long long)enc_max(v));
                 break;
             case AMD_AGG_COUNT_DISTINCT:
+            case AMD_AGG_MEDIAN:
+            case AMD_AGG_MIN_RETRACT:
+            case AMD_AGG_MAX_RETRACT:
                 chain_add(A.store, slot, a, v, d, A.err);
                 break;
             case AMD_AGG_STDDEV:
@@ -401,6 +433,265 @@ __device__ inline void ueval_slot(const UStore &S, const AggSpec &agg,
             out[a] = cnt;
             break;
         }
+        case AMD_AGG_MEDIAN:
+        case AMD_AGG_MIN_RETRACT:
+        case AMD_AGG_MAX_RETRACT:
+            /* selected by k_updagg_ordstat earlier in this flush, for
+             * exactly the slots that reach this point */
+            out[a] = S.ord[(size_t)slot * agg.n_aggs + a];
+            break;
+        }
+    }
+}
+
+/* ---- order statistics (MEDIAN, MIN_RETRACT, MAX_RETRACT) at flush ----
+ *
+ * One wavefront per changed (slot, ordered aggregate).  LDS per wave: a
+ * tile of UORD_TILE (encoded value, net count) entries = 256 * 16 B = 4 KB,
+ * plus a 256-bin i64 histogram = 2 KB; a 256-thread workgroup (4 waves)
+ * holds 24 KB, so LDS admits 6 workgroups = 24 waves per CU of the 160 KB.
+ * Chains with more than UORD_TILE live nodes go to a global arena of
+ * pool_cap entries: every chain is visited once per flush and chains are
+ * disjoint, so a per-flush bump allocation cannot exceed the pool size. */
+#define UORD_TILE 256
+#define UORD_WAVES 4
+
+struct OrdEnt {
+    uint64_t enc;         /* enc_max(value): unsigned order == i64 order */
+    long long net;        /* this node's share of the value's refcount */
+};
+
+struct OrdArgs {
+    UStore store;
+    AggSpec agg;
+    uint32_t cur_epoch;
+    OrdEnt *arena;
+    unsigned long long *arena_cur;
+    int64_t arena_cap;
+    int *err;
+};
+
+/* one wave's LDS phases are ordered by this; waves of a workgroup run
+ * independent trip counts, so no workgroup barrier may be used here */
+__device__ __forceinline__ void wave_sync() {
+    __threadfence_block();
+    __builtin_amdgcn_wave_barrier();
+}
+
+/* Element of rank r (0-based) of the multiset {ent[i].enc weighted by
+ * ent[i].net}, by MSB-first radix select.  Every loop is bounded by n or a
+ * constant whatever the weights are; *bad is set when no bin holds r
+ * (possible only when a value's summed net is negative).  All entries agree
+ * on the bytes above ptop (prefix0 holds them), so the passes start at byte
+ * ptop; ptop < 0 means a single value. */
+__device__ __forceinline__ uint64_t ord_select(const volatile OrdEnt *ent,
+                                               int64_t n, long long r,
+                                               uint64_t prefix0, int ptop,
+                                               long long *hist, int lane,
+                                               bool *bad) {
+    uint64_t prefix = prefix0;
+    for (int p = ptop; p >= 0; p--) {
+        int sh = p * 8;
+        uint64_t himask = p == 7 ? 0ULL : ~0ULL << (sh + 8);
+        for (int b = lane; b < 256; b += 64) hist[b] = 0;
+        wave_sync();
+        for (int64_t i = lane; i < n; i += 64) {
+            uint64_t e = ent[i].enc;
+            long long w = ent[i].net;
+            if (((e ^ prefix) & himask) == 0)
+                atomicAdd((unsigned long long *)&hist[(e >> sh) & 255],
+                          (unsigned long long)w);
+        }
+        wave_sync();
+        /* lane l owns bins 4l..4l+3; wave-wide inclusive scan of the sums */
+        long long b[4], s = 0;
+        for (int k = 0; k < 4; k++) {
+            b[k] = hist[lane * 4 + k];
+            s += b[k];
+        }
+        long long inc = s;
+        for (int o = 1; o < 64; o <<= 1) {
+            long long t = __shfl_up(inc, o, 64);
+            if (lane >= o) inc += t;
+        }
+        long long c = inc - s;
+        int dsel = -1;
+        long long rsel = 0;
+        for (int k = 0; k < 4; k++) {
+            if (dsel < 0 && r >= c && r < c + b[k]) {
+                dsel = lane * 4 + k;
+                rsel = r - c;
+            }
+            c += b[k];
+        }
+        unsigned long long m = __ballot(dsel >= 0);
+        wave_sync();   /* hist is rewritten by the next pass */
+        if (!m) {
+            *bad = true;
+            return prefix;
+        }
+        int src = (int)__ffsll((long long)m) - 1;
+        int d = __shfl(dsel, src, 64);
+        r = __shfl(rsel, src, 64);
+        prefix |= (uint64_t)d << sh;
+    }
+    return prefix;
+}
+
+/* (lo + hi) / 2 truncated toward zero, without 64-bit overflow */
+__host__ __device__ inline int64_t ord_midpoint(int64_t lo, int64_t hi) {
+    int64_t s = lo / 2 + hi / 2;
+    int rr = (int)(lo % 2) + (int)(hi % 2);   /* -2..2 */
+    if (rr == 2) return s + 1;
+    if (rr == -2) return s - 1;
+    if (rr == 1) return s >= 0 ? s : s + 1;
+    if (rr == -1) return s > 0 ? s - 1 : s;
+    return s;
+}
+
+__global__ void __launch_bounds__(64 * UORD_WAVES)
+k_updagg_ordstat(OrdArgs A) {
+    __shared__ OrdEnt tile_all[UORD_WAVES][UORD_TILE];
+    __shared__ long long hist_all[UORD_WAVES][256];
+    const UStore &S = A.store;
+    int na = A.agg.n_aggs;
+    int lane = (int)(threadIdx.x & 63);
+    int wv = (int)(threadIdx.x >> 6);
+    OrdEnt *tile = tile_all[wv];
+    long long *hist = hist_all[wv];
+    /* per-op bit masks over the aggregate index (no indexed reads of the
+     * kernel-argument arrays by a lane-varying index) */
+    unsigned med = 0, mn = 0, mx = 0;
+    for (int k = 0; k < AMD_MAX_AGGS; k++) {
+        if (k >= na) break;
+        if (A.agg.op[k] == AMD_AGG_MEDIAN) med |= 1u << k;
+        if (A.agg.op[k] == AMD_AGG_MIN_RETRACT) mn |= 1u << k;
+        if (A.agg.op[k] == AMD_AGG_MAX_RETRACT) mx |= 1u << k;
+    }
+    unsigned ordm = med | mn | mx;
+    int64_t n_slots = (int64_t)S.C + 1;
+    int64_t wave_id = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / 64;
+    int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) / 64;
+    /* a wave scans 8 slots x 8 aggregate columns per step: lane = (slot
+     * offset, aggregate), the layout of the head plane.  Untouched slots
+     * are rejected on the epoch word alone. */
+    int sub = lane >> 3, la = lane & 7;
+    for (int64_t ws = wave_id * 8; ws < n_slots; ws += n_waves * 8) {
+        int64_t lslot = ws + sub;
+        bool want = false;
+        int32_t lhead = -1;
+        if (lslot < n_slots && ((ordm >> la) & 1) &&
+            S.epoch[lslot] == A.cur_epoch &&
+            (lslot == (int64_t)S.C || S.keys[lslot] != EMPTY_KEY) &&
+            S.rows[lslot] > 0) {
+            want = true;
+            lhead = S.head[(size_t)lslot * 8 + la];
+        }
+        unsigned long long todo = __ballot(want);
+        while (todo) {
+            int src = (int)__ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            int64_t slot = ws + (src >> 3);
+            int a = src & 7;
+            int32_t head = __shfl(lhead, src, 64);
+            /* gather: every lane walks the same chain (broadcast loads),
+             * lane 0 stores the live nodes.  Steps are bounded by the
+             * pool size and every index is range-checked, so a corrupt
+             * link ends the walk instead of running away. */
+            int64_t n = 0, steps = 0;
+            long long W = 0;
+            uint64_t first = 0, diff = 0;   /* bits in which entries differ */
+            bool bad = false;
+            for (int32_t j = head; j >= 0;) {
+                if ((int64_t)j >= S.pool_cap || steps >= S.pool_cap) {
+                    bad = true;
+                    break;
+                }
+                steps++;
+                int64_t v = S.pool[j].value;
+                long long d = S.pool[j].delta;
+                j = S.pool[j].next;
+                if (d == 0) continue;          /* fully retracted value */
+                uint64_t e = enc_max(v);
+                if (n < UORD_TILE && lane == 0) {
+                    tile[n].enc = e;
+                    tile[n].net = d;
+                }
+                if (n == 0) first = e;
+                diff |= e ^ first;
+                W += d;
+                n++;
+            }
+            const volatile OrdEnt *ent = tile;
+            if (!bad && n > UORD_TILE) {
+                /* wide chain: second walk into the global arena */
+                unsigned long long base = 0;
+                if (lane == 0)
+                    base = atomicAdd(A.arena_cur, (unsigned long long)n);
+                base = (unsigned long long)__shfl((long long)base, 0, 64);
+                if ((int64_t)base + n > A.arena_cap) {
+                    bad = true;
+                } else {
+                    OrdEnt *dst = A.arena + base;
+                    int64_t i = 0;
+                    steps = 0;
+                    for (int32_t j = head; j >= 0 && i < n;) {
+                        if ((int64_t)j >= S.pool_cap ||
+                            steps >= S.pool_cap) {
+                            bad = true;
+                            break;
+                        }
+                        steps++;
+                        int64_t v = S.pool[j].value;
+                        long long d = S.pool[j].delta;
+                        j = S.pool[j].next;
+                        if (d == 0) continue;
+                        if (lane == 0) {
+                            dst[i].enc = enc_max(v);
+                            dst[i].net = d;
+                        }
+                        i++;
+                    }
+                    if (i != n) bad = true;
+                    __threadfence();
+                    ent = dst;
+                }
+            }
+            wave_sync();
+            int64_t res = 0;
+            if (bad) {
+                if (lane == 0) *A.err = UERR_ORD_CHAIN;
+            } else if (W != S.rows[slot]) {
+                /* W <= 0 lands here too: rows > 0 for every slot taken */
+                if (lane == 0) *A.err = UERR_ORD_ROWS;
+            } else {
+                bool sbad = false;
+                /* skip the radix passes over bytes every entry shares
+                 * (small-range columns differ in the low byte or two) */
+                int ptop = diff ? (63 - __clzll((long long)diff)) >> 3 : -1;
+                uint64_t pre =
+                    ptop == 7 ? 0ULL : first & (~0ULL << ((ptop + 1) * 8));
+                if ((mn >> a) & 1) {
+                    res = dec_max(
+                        ord_select(ent, n, 0, pre, ptop, hist, lane, &sbad));
+                } else if ((mx >> a) & 1) {
+                    res = dec_max(ord_select(ent, n, W - 1, pre, ptop, hist,
+                                             lane, &sbad));
+                } else {
+                    int64_t hi = dec_max(ord_select(ent, n, W / 2, pre, ptop,
+                                                    hist, lane, &sbad));
+                    res = hi;
+                    if (!(W & 1)) {
+                        int64_t lo =
+                            dec_max(ord_select(ent, n, (W - 1) / 2, pre,
+                                               ptop, hist, lane, &sbad));
+                        res = ord_midpoint(lo, hi);
+                    }
+                }
+                if (sbad && lane == 0) *A.err = UERR_ORD_ROWS;
+            }
+            if (lane == 0) S.ord[(size_t)slot * na + a] = res;
+            wave_sync();   /* tile is rewritten by the next item */
         }
     }
 }
@@ -581,7 +872,11 @@ k_updagg_drain(UDrainArgs D) {
                 D.out[col++][r] = S.last[(size_t)slot * na + a];
         } else {
             for (int a = 0; a < na; a++) {
-                if (D.agg.op[a] != AMD_AGG_COUNT_DISTINCT) continue;
+                if (D.agg.op[a] != AMD_AGG_COUNT_DISTINCT &&
+                    D.agg.op[a] != AMD_AGG_MEDIAN &&
+                    D.agg.op[a] != AMD_AGG_MIN_RETRACT &&
+                    D.agg.op[a] != AMD_AGG_MAX_RETRACT)
+                    continue;
                 for (int32_t i = S.head[(size_t)slot * 8 + a]; i >= 0;
                      i = S.pool[i].next) {
                     if (S.pool[i].delta == 0) continue;
@@ -654,11 +949,19 @@ struct GpuUpdAgg {
     int64_t stg_cap;
     int n_in_cols, out_cols, drain0_cols, drain1_cols;
     int64_t out_cap;
+    int has_ord;                /* config has MEDIAN / MIN_RETRACT / MAX_RETRACT */
+    OrdEnt *d_arena;            /* [pool_cap] wide-chain scratch (has_ord) */
+    unsigned long long *d_arena_cur;
     hipStream_t stream;
     char err_msg[512];
 };
 
-#define UHIP(o, call)                                                         \
+static bool ua_is_ord(int op) {
+    return op == AMD_AGG_MEDIAN || op == AMD_AGG_MIN_RETRACT ||
+           op == AMD_AGG_MAX_RETRACT;
+}
+
+#define UHIP(o, call)                                                        \
     do {                                                                      \
         hipError_t _e = (call);                                               \
         if (_e != hipSuccess) {                                               \
@@ -675,8 +978,27 @@ API void *arroyo_amd_updagg_create(const AmdUpdatingConfig *cfg) {
         snprintf(g_ua_err, sizeof g_ua_err, "invalid updagg config");
         return nullptr;
     }
+    int has_ord = 0;
+    for (int i = 0; i < cfg->n_aggs; i++) {
+        int op = cfg->agg_ops[i];
+        if (op < AMD_AGG_COUNT || op > AMD_AGG_MAX_RETRACT) {
+            snprintf(g_ua_err, sizeof g_ua_err,
+                     "invalid updagg config: unknown aggregate op %d", op);
+            return nullptr;
+        }
+        if (ua_is_ord(op)) {
+            if (cfg->agg_col[i] < 0 || cfg->agg_col[i] >= cfg->n_value_cols) {
+                snprintf(g_ua_err, sizeof g_ua_err,
+                         "invalid updagg config: aggregate op %d needs a "
+                         "value column", op);
+                return nullptr;
+            }
+            has_ord = 1;
+        }
+    }
     GpuUpdAgg *o = new GpuUpdAgg();
     o->cfg = *cfg;
+    o->has_ord = has_ord;
     o->agg.n_aggs = cfg->n_aggs;
     o->agg.SW = 0;
     for (int i = 0; i < cfg->n_aggs; i++) {
@@ -736,6 +1058,13 @@ API void *arroyo_amd_updagg_create(const AmdUpdatingConfig *cfg) {
     UALLOC(o->store.head, C1 * 8 * 4);
     UALLOC(o->store.pool, (size_t)o->store.pool_cap * sizeof(Node));
     UALLOC(o->store.pool_cur, 8);
+    if (o->has_ord) {
+        /* no reset needed between flushes: k_updagg_ordstat writes ord for
+         * exactly the (slot, agg) pairs k_updagg_flush then reads */
+        UALLOC(o->store.ord, C1 * na * 8);
+        UALLOC(o->d_arena, (size_t)o->store.pool_cap * sizeof(OrdEnt));
+        UALLOC(o->d_arena_cur, 8);
+    }
     int max_out = o->drain0_cols;
     if (o->drain1_cols > max_out) max_out = o->drain1_cols;
     if (o->out_cols > max_out) max_out = o->out_cols;
@@ -787,6 +1116,10 @@ static int ua_check_err(GpuUpdAgg *o) {
         : e == UERR_OUT_CAP ? "output buffer full; raise log2_out_cap"
         : e == UERR_RETRACT
             ? "MIN/MAX do not support retraction (append-only here)"
+        : e == UERR_ORD_ROWS
+            ? "ordered aggregate: retraction without a matching append"
+        : e == UERR_ORD_CHAIN
+            ? "ordered aggregate: value chain exceeds the node pool"
             : "device error";
     snprintf(o->err_msg, sizeof o->err_msg, "%s", msg);
     return 1;
@@ -862,6 +1195,22 @@ API int arroyo_amd_updagg_flush(void *h, AmdOutBatch *out) {
     GpuUpdAgg *o = (GpuUpdAgg *)h;
     if (ua_check_err(o)) return 1;
     UHIP(o, hipMemsetAsync(o->d_n_out, 0, 8, o->stream));
+    if (o->has_ord) {
+        /* order-statistic pre-pass: one wave per 8 slots, grid-strided */
+        UHIP(o, hipMemsetAsync(o->d_arena_cur, 0, 8, o->stream));
+        OrdArgs R = {};
+        R.store = o->store;
+        R.agg = o->agg;
+        R.cur_epoch = o->cur_epoch;
+        R.arena = o->d_arena;
+        R.arena_cur = o->d_arena_cur;
+        R.arena_cap = o->store.pool_cap;
+        R.err = o->d_err;
+        int64_t waves = ((int64_t)o->store.C + 1 + 7) / 8;
+        hipLaunchKernelGGL(k_updagg_ordstat, dim3(ua_grid(waves * 64)),
+                           dim3(64 * UORD_WAVES), 0, o->stream, R);
+        UHIP(o, hipGetLastError());
+    }
     FlushArgs F = {};
     F.store = o->store;
     F.agg = o->agg;
@@ -1044,6 +1393,11 @@ API void arroyo_amd_updagg_destroy(void *h) {
     hipFree(o->store.head);
     hipFree(o->store.pool);
     hipFree(o->store.pool_cur);
+    if (o->has_ord) {
+        hipFree(o->store.ord);
+        hipFree(o->d_arena);
+        hipFree(o->d_arena_cur);
+    }
     int max_out = o->drain0_cols;
     if (o->drain1_cols > max_out) max_out = o->drain1_cols;
     if (o->out_cols > max_out) max_out = o->out_cols;

@@ -66,7 +66,21 @@ enum AmdAggOp {
      * words); AND = bit set in every live row, OR = in any.  bool_and /
      * bool_or are these over a 0/1 column. */
     AMD_AGG_BIT_AND = 23,
-    AMD_AGG_BIT_OR = 24
+    AMD_AGG_BIT_OR = 24,
+    /* order statistics under retraction (updating aggregate only; the
+     * window, session and join operators reject them at create).  i64
+     * input column, i64 output.  Each keeps the key's exact value multiset
+     * (as COUNT DISTINCT does) and is selected from it at flush.
+     * MEDIAN over the live multiset M of size W, sorted: odd W gives
+     * M[W/2]; even W gives (M[(W-1)/2] + M[W/2]) / 2 in exact integer
+     * arithmetic truncated toward zero, computed without 64-bit overflow
+     * (DataFusion's integer median wherever its add does not wrap).
+     * MIN_RETRACT / MAX_RETRACT are the retract-capable forms of MIN / MAX
+     * a planner picks when the input is updating; AMD_AGG_MIN / MAX keep
+     * their one-word append-only fast path. */
+    AMD_AGG_MEDIAN = 25,
+    AMD_AGG_MIN_RETRACT = 26,
+    AMD_AGG_MAX_RETRACT = 27
 };
 
 #define AMD_MAX_AGGS 8
@@ -212,10 +226,15 @@ typedef struct {
  * when the value did not change.  COUNT/SUM/AVG retract by subtraction
  * (the reference's Sliding accumulators); COUNT DISTINCT keeps an exact
  * per-key value multiset (the reference's Batch accumulator,
- * IncrementalState::Batch :84-174); MIN/MAX are append-only here (the
- * reference re-aggregates a stored multiset on demand; unsupported-retract
- * is a loud error).  Flush cadence is driven by the caller (the reference's
- * tick timer). */
+ * IncrementalState::Batch :84-174); AMD_AGG_MIN / AMD_AGG_MAX are the
+ * append-only one-word fast path (a retraction on them is a loud error);
+ * AMD_AGG_MIN_RETRACT / AMD_AGG_MAX_RETRACT / AMD_AGG_MEDIAN keep the same
+ * per-key value multiset as COUNT DISTINCT and re-select from it at flush,
+ * which is what the reference's Batch accumulator does for min/max/median
+ * over an updating input.  Their cost is linear in the distinct values a
+ * key has ever held (log2_nodes bounds the pool; zero-net nodes are not
+ * reclaimed).  Unknown op codes are rejected at create.  Flush cadence is
+ * driven by the caller (the reference's tick timer). */
 typedef struct {
     int32_t  n_keys;            /* 0 or 1 */
     int32_t  n_value_cols;

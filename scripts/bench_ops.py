@@ -142,12 +142,78 @@ def bench_updagg_device():
           f"{dt*1e6/batches:.0f} us per 1M-row batch)")
 
 
+def bench_ordered(which=("A", "B"), reps=10, warmup=2):
+    """Updating aggregate with per-key value multisets: 2^16 keys x ~100
+    distinct values per key.  Config A = COUNT + COUNT DISTINCT (no
+    order-statistic pre-pass is launched), B = A + MEDIAN + MIN_RETRACT +
+    MAX_RETRACT.  Times are host-clock around calls that end in a stream
+    synchronise (the operator owns its stream).  Every timed flush follows a
+    one-row-per-key batch, so it re-evaluates all 2^16 keys."""
+    import json
+    from arroyo_amd import cabi, gpu
+    n_keys = 1 << 16
+    per_key = 256
+    n = 1 << 20
+    rng = np.random.default_rng(6)
+    total = n_keys * per_key
+    key = rng.permutation(np.repeat(np.arange(n_keys, dtype=np.int64),
+                                    per_key))
+    val = rng.integers(0, 100, size=total).astype(np.int64)
+    zeros = np.zeros(n, dtype=np.int64)
+    tkey = np.arange(n_keys, dtype=np.int64)
+    aggs = {"A": [(cabi.COUNT, -1), (cabi.COUNT_DISTINCT, 0)]}
+    aggs["B"] = aggs["A"] + [(cabi.MEDIAN, 0), (cabi.MIN_RETRACT, 0),
+                             (cabi.MAX_RETRACT, 0)]
+    for name in which:
+        op = gpu.make_updagg_op(cabi.make_updagg_config(
+            aggs[name], n_keys=1, n_value_cols=1, log2_capacity=17,
+            log2_nodes=23 if name == "A" else 25, log2_out_cap=18))
+        upd = []
+        for lo in range(0, total, n):
+            t0 = time.perf_counter()
+            op.process_batch([key[lo:lo + n], val[lo:lo + n], zeros])
+            upd.append((time.perf_counter() - t0) * 1e3)
+        op.flush()
+        fl = []
+        for i in range(warmup + reps):
+            tv = rng.integers(0, 100, size=n_keys).astype(np.int64)
+            op.process_batch([tkey, tv, zeros[:n_keys]])
+            t0 = time.perf_counter()
+            out = op.flush()
+            fl.append((time.perf_counter() - t0) * 1e3)
+            assert len(out[0]) == 2 * n_keys   # every key re-emitted
+        op.close()
+        upd, fl = upd[warmup:], fl[warmup:]
+        res = {"leg": "ordered", "config": name, "keys": n_keys,
+               "rows": total,
+               "update_ms_per_1M_median": float(np.median(upd)),
+               "update_ms_per_1M_min": float(np.min(upd)),
+               "update_ms_per_1M_max": float(np.max(upd)),
+               "flush_ms_median": float(np.median(fl)),
+               "flush_ms_min": float(np.min(fl)),
+               "flush_ms_max": float(np.max(fl))}
+        print(f"ordered {name}: update {res['update_ms_per_1M_median']:.2f} "
+              f"ms per 1M-row batch (incl. H2D staging), flush of 2^16 "
+              f"changed keys {res['flush_ms_median']:.2f} ms "
+              f"(min {res['flush_ms_min']:.2f}, max {res['flush_ms_max']:.2f}"
+              f", incl. D2H of the emitted rows)")
+        print(json.dumps(res))
+
+
+LEGS = {"expjoin": bench_expjoin, "updagg": bench_updagg,
+        "expjoin_device": bench_expjoin_device,
+        "updagg_device": bench_updagg_device, "ordered": bench_ordered}
+
+
 if __name__ == "__main__":
     # torch's bundled HIP runtime must initialize before the op library's
     # (system-ROCm) runtime touches the device, or torch.cuda breaks
     import torch
     torch.zeros(1, device="cuda")
-    bench_expjoin()
-    bench_updagg()
-    bench_expjoin_device()
-    bench_updagg_device()
+    # python scripts/bench_ops.py [leg ...]; "ordered:A" runs one config
+    for arg in sys.argv[1:] or list(LEGS):
+        leg, _, cfgs = arg.partition(":")
+        if cfgs:
+            LEGS[leg](which=tuple(cfgs.split(",")))
+        else:
+            LEGS[leg]()
