@@ -140,6 +140,14 @@ def out_validity(out):
     return masks
 
 
+def pack_validity(mask):
+    """Pack a bool mask into an Arrow validity bitmap (LSB bit order, bit
+    offset 0, (n + 7) // 8 bytes, padding bits clear): the inverse of
+    :func:`out_validity`."""
+    mask = np.ascontiguousarray(mask, dtype=bool)
+    return np.packbits(mask, bitorder="little")
+
+
 def _out_to_numpy(out):
     """Copy an AmdOutBatch (host memory) into numpy arrays."""
     n = out.n_rows
@@ -754,12 +762,15 @@ class AmdUpdatingConfig(ctypes.Structure):
         ("log2_out_cap", ctypes.c_uint32),
         ("device", ctypes.c_int32),
         ("emit_to_host", ctypes.c_int32),
+        ("null_semantics", ctypes.c_int32),
     ]
 
 
 def make_updagg_config(aggs, n_keys=1, n_value_cols=0, log2_capacity=16,
                        log2_nodes=20, log2_out_cap=20, device=0,
-                       emit_to_host=True):
+                       emit_to_host=True, null_semantics=False):
+    """null_semantics=True: SQL NULL semantics (nullable value columns in,
+    validity bitmaps out; see AmdUpdatingConfig in arroyo_amd_types.h)."""
     cfg = AmdUpdatingConfig()
     cfg.n_keys = n_keys
     cfg.n_value_cols = n_value_cols
@@ -774,6 +785,7 @@ def make_updagg_config(aggs, n_keys=1, n_value_cols=0, log2_capacity=16,
     cfg.log2_out_cap = log2_out_cap
     cfg.device = device
     cfg.emit_to_host = 1 if emit_to_host else 0
+    cfg.null_semantics = 1 if null_semantics else 0
     return cfg
 
 
@@ -851,20 +863,95 @@ class UpdAggOp:
         self._check(self._fn["process_batch_device"](self._h, arr,
                                                      len(dptrs), n_rows))
 
+    def _bind_nullable(self, name):
+        """Nullable ingest is a GPU-library extension (the C oracle has no
+        NULLs): bound on first use so oracle-backed ops still construct."""
+        if name not in self._fn:
+            lib, prefix = self._fn["_lib_prefix"]
+            f = getattr(lib, prefix + "updagg_" + name)
+            f.restype = ctypes.c_int
+            f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
+                          ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
+                          ctypes.c_int64]
+            self._fn[name] = f
+        return self._fn[name]
+
+    def process_batch_nullable(self, cols, valid):
+        """cols as for process_batch; valid is None (everything valid) or a
+        list parallel to cols whose entries are None (column all valid) or
+        a bool array (True = non-null)."""
+        f = self._bind_nullable("process_batch_nullable")
+        keep, arr = _cols_to_ptrs(cols)
+        n_rows = len(keep[0]) if keep else 0
+        varr, vkeep = None, []
+        if valid is not None:
+            if len(valid) != len(keep):
+                raise ValueError(
+                    f"valid has {len(valid)} entries for {len(keep)} cols")
+            ptrs = []
+            for m in valid:
+                if m is None:
+                    ptrs.append(None)
+                    continue
+                if len(m) != n_rows:
+                    raise ValueError("validity mask length != n_rows")
+                bm = pack_validity(m)
+                if len(bm) == 0:
+                    bm = np.zeros(1, dtype=np.uint8)
+                vkeep.append(bm)
+                ptrs.append(bm.ctypes.data_as(ctypes.c_void_p).value)
+            varr = (ctypes.c_void_p * len(ptrs))(*ptrs)
+        self._check(f(self._h, arr, varr, len(keep), n_rows))
+
+    def process_batch_nullable_device(self, dptrs, dvalid_ptrs, n_rows):
+        """Device-resident nullable ingest: dptrs as for
+        process_batch_device; dvalid_ptrs is None or a list parallel to
+        dptrs of None / raw device addresses of Arrow validity bitmaps
+        (8-byte aligned, padded to a multiple of 8 bytes)."""
+        f = self._bind_nullable("process_batch_nullable_device")
+        arr = (ctypes.c_void_p * len(dptrs))(*dptrs)
+        varr = None
+        if dvalid_ptrs is not None:
+            if len(dvalid_ptrs) != len(dptrs):
+                raise ValueError(
+                    f"dvalid_ptrs has {len(dvalid_ptrs)} entries for "
+                    f"{len(dptrs)} cols")
+            varr = (ctypes.c_void_p * len(dvalid_ptrs))(*dvalid_ptrs)
+        self._check(f(self._h, arr, varr, len(dptrs), n_rows))
+
+    def _take_out(self, out, with_validity):
+        cols = _out_to_numpy(out)
+        masks = out_validity(out) if with_validity else None
+        self._fn["free_out"](ctypes.byref(out))
+        if not with_validity:
+            return cols
+        n = len(cols[0]) if cols else 0
+        masks = [np.ones(n, dtype=bool) if m is None else m for m in masks]
+        return cols, masks
+
     def flush(self):
         out = AmdOutBatch()
         self._check(self._fn["flush"](self._h, ctypes.byref(out)))
-        cols = _out_to_numpy(out)
-        self._fn["free_out"](ctypes.byref(out))
-        return cols
+        return self._take_out(out, False)
+
+    def flush_with_validity(self):
+        """flush() plus the per-column validity as bool masks (all True for
+        a column without a bitmap): returns (cols, masks)."""
+        out = AmdOutBatch()
+        self._check(self._fn["flush"](self._h, ctypes.byref(out)))
+        return self._take_out(out, True)
 
     def expire(self, idle_flushes):
         out = AmdOutBatch()
         self._check(self._fn["expire"](self._h, idle_flushes,
                                        ctypes.byref(out)))
-        cols = _out_to_numpy(out)
-        self._fn["free_out"](ctypes.byref(out))
-        return cols
+        return self._take_out(out, False)
+
+    def expire_with_validity(self, idle_flushes):
+        out = AmdOutBatch()
+        self._check(self._fn["expire"](self._h, idle_flushes,
+                                       ctypes.byref(out)))
+        return self._take_out(out, True)
 
     def checkpoint_drain(self, which):
         out = AmdOutBatch()

@@ -40,6 +40,16 @@
  *     retract(last) + append(new) (retract-only on deletion, nothing when
  *     unchanged) through a wave-aggregated output cursor; the retract row
  *     always directly precedes its append row.
+ *   - SQL NULLs are opt-in (AmdUpdatingConfig.null_semantics = 1): value
+ *     columns arrive with Arrow validity bitmaps, k_updagg_update_nullable
+ *     skips an aggregate's atomics where its argument is NULL and keeps a
+ *     per-aggregate non-null count, flush decides NULL from that count (or
+ *     from the condition under which the result is undefined) and emits a
+ *     validity mask per row, and k_updagg_pack_validity ballots the masks
+ *     into per-column Arrow bitmaps on the device.  With the option off
+ *     the non-nullable kernels run, instantiated from the same source.
+ *     The C oracle has no NULLs: tests/test_null_aggs.py compares against
+ *     a Python model of DataFusion's accumulator rule.
  *
  * Parity is pinned against oracle/arroyo_oracle.c (itself pinned against
  * the reference's debezium_agg / filter_updating_aggregates golden
@@ -201,8 +211,42 @@ __device__ inline void fold_f64(uint64_t *w, double dv) {
     } while (old != assumed);
 }
 
-__global__ void __launch_bounds__(256)
-k_updagg_update(UpdateArgs A) {
+/* ---- SQL NULL semantics (AmdUpdatingConfig.null_semantics == 1) ----
+ *
+ * Every aggregate keeps n_a, its count of live contributing rows (argument
+ * non-null; both arguments for the co-moment family), in one state word:
+ * COUNT(col) and AVG already hold it in st[0] (COUNT(*) counts every row,
+ * so it reads the key's row count and keeps no state); the one-word and
+ * chained states use their spare st[1]; the moment, co-moment and bit
+ * states grow by one trailing word.  ua_noff is that word's offset within the aggregate's
+ * state, ua_width the state width. */
+__host__ __device__ inline bool ua_is_comoment(int op) {
+    return op >= AMD_AGG_COVAR_POP && op <= AMD_AGG_REGR_SXY;
+}
+__host__ __device__ inline int ua_noff(int op) {
+    if (op == AMD_AGG_COUNT || op == AMD_AGG_AVG) return 0;
+    if (op >= AMD_AGG_STDDEV && op <= AMD_AGG_VAR_POP) return 2;
+    if (ua_is_comoment(op)) return 5;
+    if (op == AMD_AGG_BIT_AND || op == AMD_AGG_BIT_OR) return 32;
+    return 1;
+}
+__host__ __device__ inline int ua_width(int op, int null_semantics) {
+    int w = 2;
+    if (ua_is_comoment(op)) w = 5;
+    else if (op == AMD_AGG_BIT_AND || op == AMD_AGG_BIT_OR) w = 32;
+    if (null_semantics && ua_noff(op) >= w) w = ua_noff(op) + 1;
+    return w;
+}
+
+/* The update loop.  NS = false is the non-nullable kernel; NS = true reads
+ * each value column's Arrow validity bitmap as 64-bit words (the 64
+ * consecutive rows of a wavefront share one word per column: blocks are 256
+ * threads and the grid stride a multiple of 256, so a wave's first row is a
+ * multiple of 64), skips the atomics of an aggregate whose argument is
+ * null, and counts the contributing rows in the aggregate's n_a word. */
+template <bool NS>
+__device__ __forceinline__ void update_rows(const UpdateArgs &A,
+                                            const uint64_t *const *valid) {
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const int64_t *retr = A.cols[A.n_keys + A.n_vals];
     for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -214,11 +258,38 @@ k_updagg_update(UpdateArgs A) {
         A.store.epoch[slot] = A.cur_epoch;
         atomicAdd((unsigned long long *)&A.store.rows[slot],
                   (unsigned long long)d);
+        unsigned vm = 0xFFu;   /* bit c: value column c is non-null */
+        if constexpr (NS) {
+            for (int c = 0; c < A.n_vals; c++) {
+                const uint64_t *bm = valid[c];
+                if (bm && !((bm[r >> 6] >> (r & 63)) & 1)) vm &= ~(1u << c);
+            }
+        }
         uint64_t *stp = A.store.st + (size_t)slot * A.agg.SW;
         for (int a = 0; a < A.agg.n_aggs; a++) {
             int64_t v = A.agg.col[a] >= 0
                             ? A.cols[A.n_keys + A.agg.col[a]][r] : 0;
             uint64_t *st = stp + A.agg.soff[a];
+            if constexpr (NS) {
+                int op = A.agg.op[a];
+                /* COUNT(*) is the key's live row count, already kept in
+                 * rows[slot]: no second atomic for it */
+                if (op == AMD_AGG_COUNT && A.agg.col[a] < 0) continue;
+                bool ok = A.agg.col[a] < 0 || ((vm >> A.agg.col[a]) & 1);
+                if (ua_is_comoment(op))
+                    ok = ok && ((vm >> A.agg.col2[a]) & 1);
+                if (!ok) {
+                    /* append-only MIN/MAX reject a retraction whatever the
+                     * retracted value is */
+                    if ((op == AMD_AGG_MIN || op == AMD_AGG_MAX) && d < 0)
+                        *A.err = UERR_RETRACT;
+                    continue;
+                }
+                /* COUNT and AVG count n_a in st[0] themselves */
+                if (ua_noff(op) != 0)
+                    atomicAdd((unsigned long long *)&st[ua_noff(op)],
+                              (unsigned long long)d);
+            }
             switch (A.agg.op[a]) {
             case AMD_AGG_COUNT:
                 atomicAdd((unsigned long long *)&st[0],
@@ -292,34 +363,71 @@ k_updagg_update(UpdateArgs A) {
     }
 }
 
+__global__ void __launch_bounds__(256)
+k_updagg_update(UpdateArgs A) {
+    update_rows<false>(A, nullptr);
+}
+
+struct UpdateArgsN {
+    UpdateArgs A;
+    const uint64_t *valid[8];  /* per value column; null = all valid */
+};
+
+__global__ void __launch_bounds__(256)
+k_updagg_update_nullable(UpdateArgsN N) {
+    update_rows<true>(N.A, N.valid);
+}
+
 /* evaluate one key's current values into out[n_aggs] (i64 / f64-bits).
  * COUNT DISTINCT walks the chain, summing per-value deltas with an in-chain
  * dedup (duplicate nodes from racing first-inserts are rare and benign). */
+/* NS (null semantics): n_a replaces the key's row count wherever an
+ * aggregate uses n, *vmask gets bit a set when aggregate a is non-NULL, and
+ * the value under a NULL is 0.  NULL is decided from the condition (n_a == 0
+ * or the result undefined), never by testing the result for NaN. */
+template <bool NS>
 __device__ inline void ueval_slot(const UStore &S, const AggSpec &agg,
-                                  int64_t slot, int64_t *out) {
+                                  int64_t slot, int64_t *out,
+                                  unsigned *vmask) {
     const uint64_t *stp = S.st + (size_t)slot * agg.SW;
+    unsigned vm = 0;
     for (int a = 0; a < agg.n_aggs; a++) {
         const uint64_t *st = stp + agg.soff[a];
+        bool ok = true;   /* NS: aggregate a is non-NULL */
+        long long na_rows = 0;
+        if constexpr (NS) na_rows = (long long)st[ua_noff(agg.op[a])];
         switch (agg.op[a]) {
         case AMD_AGG_COUNT:
+            /* NS: COUNT(*) keeps no state of its own (see update_rows) */
+            out[a] = NS && agg.col[a] < 0 ? (int64_t)S.rows[slot]
+                                          : (int64_t)st[0];
+            break;
         case AMD_AGG_SUM:
             out[a] = (int64_t)st[0];
+            if constexpr (NS) ok = na_rows > 0;
             break;
-        case AMD_AGG_MIN: out[a] = dec_min(st[0]); break;
-        case AMD_AGG_MAX: out[a] = dec_max(st[0]); break;
+        case AMD_AGG_MIN:
+            out[a] = dec_min(st[0]);
+            if constexpr (NS) ok = na_rows > 0;
+            break;
+        case AMD_AGG_MAX:
+            out[a] = dec_max(st[0]);
+            if constexpr (NS) ok = na_rows > 0;
+            break;
         case AMD_AGG_AVG: {
             double sum;
             uint64_t w1 = st[1];
             memcpy(&sum, &w1, 8);
             double v = sum / (double)(int64_t)st[0];
             memcpy(&out[a], &v, 8);
+            if constexpr (NS) ok = na_rows > 0;
             break;
         }
         case AMD_AGG_STDDEV:
         case AMD_AGG_STDDEV_POP:
         case AMD_AGG_VAR:
         case AMD_AGG_VAR_POP: {
-            double n = (double)S.rows[slot];
+            double n = NS ? (double)na_rows : (double)S.rows[slot];
             double sx, sxx;
             uint64_t w0 = st[0], w1 = st[1];
             memcpy(&sx, &w0, 8);
@@ -334,10 +442,12 @@ __device__ inline void ueval_slot(const UStore &S, const AggSpec &agg,
                 agg.op[a] == AMD_AGG_STDDEV_POP)
                 var = sqrt(var);
             memcpy(&out[a], &var, 8);
+            if constexpr (NS) ok = samp ? n > 1.0 : n > 0.0;
             break;
         }
         case AMD_AGG_BIT_XOR:
             out[a] = (int64_t)st[0];
+            if constexpr (NS) ok = na_rows > 0;
             break;
         case AMD_AGG_COVAR_POP: case AMD_AGG_COVAR_SAMP:
         case AMD_AGG_CORR: case AMD_AGG_REGR_SLOPE:
@@ -345,7 +455,7 @@ __device__ inline void ueval_slot(const UStore &S, const AggSpec &agg,
         case AMD_AGG_REGR_AVGX: case AMD_AGG_REGR_AVGY:
         case AMD_AGG_REGR_COUNT: case AMD_AGG_REGR_SXX:
         case AMD_AGG_REGR_SYY: case AMD_AGG_REGR_SXY: {
-            double n = (double)S.rows[slot];
+            double n = NS ? (double)na_rows : (double)S.rows[slot];
             double w[5];
             for (int k = 0; k < 5; k++) {
                 uint64_t b = st[k];
@@ -385,15 +495,31 @@ __device__ inline void ueval_slot(const UStore &S, const AggSpec &agg,
             default: v = 0.0; break;
             }
             if (agg.op[a] == AMD_AGG_REGR_COUNT)
-                out[a] = (int64_t)S.rows[slot];
+                out[a] = NS ? (int64_t)na_rows : (int64_t)S.rows[slot];
             else
                 memcpy(&out[a], &v, 8);
+            if constexpr (NS) {
+                /* the conditions under which v above is the NaN filler */
+                switch (agg.op[a]) {
+                case AMD_AGG_REGR_COUNT: break;
+                case AMD_AGG_COVAR_SAMP: ok = n > 1.0; break;
+                case AMD_AGG_CORR:
+                    ok = n > 1.0 && Sxx > 0.0 && Syy > 0.0;
+                    break;
+                case AMD_AGG_REGR_SLOPE:
+                case AMD_AGG_REGR_INTERCEPT:
+                case AMD_AGG_REGR_R2:
+                    ok = n > 0.0 && Sxx > 0.0;
+                    break;
+                default: ok = n > 0.0; break;
+                }
+            }
             break;
         }
         case AMD_AGG_BIT_AND:
         case AMD_AGG_BIT_OR: {
             const unsigned int *cnt = (const unsigned int *)st;
-            long long rows = S.rows[slot];
+            long long rows = NS ? na_rows : S.rows[slot];
             uint64_t r2 = 0;
             for (int b = 0; b < 64; b++) {
                 unsigned int nb = cnt[b];
@@ -403,6 +529,7 @@ __device__ inline void ueval_slot(const UStore &S, const AggSpec &agg,
                 if (set) r2 |= 1ULL << b;
             }
             out[a] = (int64_t)r2;
+            if constexpr (NS) ok = rows > 0;
             break;
         }
         case AMD_AGG_COUNT_DISTINCT: {
@@ -437,11 +564,18 @@ __device__ inline void ueval_slot(const UStore &S, const AggSpec &agg,
         case AMD_AGG_MIN_RETRACT:
         case AMD_AGG_MAX_RETRACT:
             /* selected by k_updagg_ordstat earlier in this flush, for
-             * exactly the slots that reach this point */
-            out[a] = S.ord[(size_t)slot * agg.n_aggs + a];
+             * exactly the slots that reach this point (NS: for the
+             * (slot, aggregate) pairs with n_a > 0) */
+            if constexpr (NS) ok = na_rows > 0;
+            if (ok) out[a] = S.ord[(size_t)slot * agg.n_aggs + a];
             break;
         }
+        if constexpr (NS) {
+            if (ok) vm |= 1u << a;
+            else out[a] = 0;
+        }
     }
+    if constexpr (NS) *vmask = vm;
 }
 
 /* ---- order statistics (MEDIAN, MIN_RETRACT, MAX_RETRACT) at flush ----
@@ -549,10 +683,13 @@ __host__ __device__ inline int64_t ord_midpoint(int64_t lo, int64_t hi) {
     return s;
 }
 
-__global__ void __launch_bounds__(64 * UORD_WAVES)
-k_updagg_ordstat(OrdArgs A) {
-    __shared__ OrdEnt tile_all[UORD_WAVES][UORD_TILE];
-    __shared__ long long hist_all[UORD_WAVES][256];
+/* NS: a (slot, aggregate) pair is selected when n_a > 0 (a key can have live
+ * rows that are all NULL in the column: no select, no error) and the
+ * multiset total is checked against n_a instead of the key's row count. */
+template <bool NS>
+__device__ __forceinline__ void ordstat_body(const OrdArgs &A,
+                                             OrdEnt (*tile_all)[UORD_TILE],
+                                             long long (*hist_all)[256]) {
     const UStore &S = A.store;
     int na = A.agg.n_aggs;
     int lane = (int)(threadIdx.x & 63);
@@ -576,16 +713,25 @@ k_updagg_ordstat(OrdArgs A) {
      * offset, aggregate), the layout of the head plane.  Untouched slots
      * are rejected on the epoch word alone. */
     int sub = lane >> 3, la = lane & 7;
+    /* this lane's n_a word: the chained states keep it at st[soff + 1] */
+    int lnoff = 0;
+    if constexpr (NS)
+        for (int k = 0; k < AMD_MAX_AGGS; k++)
+            if (k == la) lnoff = A.agg.soff[k] + 1;
     for (int64_t ws = wave_id * 8; ws < n_slots; ws += n_waves * 8) {
         int64_t lslot = ws + sub;
         bool want = false;
         int32_t lhead = -1;
+        long long lrows = 0;   /* the live count the multiset must total */
         if (lslot < n_slots && ((ordm >> la) & 1) &&
             S.epoch[lslot] == A.cur_epoch &&
-            (lslot == (int64_t)S.C || S.keys[lslot] != EMPTY_KEY) &&
-            S.rows[lslot] > 0) {
-            want = true;
-            lhead = S.head[(size_t)lslot * 8 + la];
+            (lslot == (int64_t)S.C || S.keys[lslot] != EMPTY_KEY)) {
+            lrows = NS ? (long long)S.st[(size_t)lslot * A.agg.SW + lnoff]
+                       : S.rows[lslot];
+            if (lrows > 0) {
+                want = true;
+                lhead = S.head[(size_t)lslot * 8 + la];
+            }
         }
         unsigned long long todo = __ballot(want);
         while (todo) {
@@ -594,6 +740,7 @@ k_updagg_ordstat(OrdArgs A) {
             int64_t slot = ws + (src >> 3);
             int a = src & 7;
             int32_t head = __shfl(lhead, src, 64);
+            long long rows = __shfl(lrows, src, 64);
             /* gather: every lane walks the same chain (broadcast loads),
              * lane 0 stores the live nodes.  Steps are bounded by the
              * pool size and every index is range-checked, so a corrupt
@@ -661,7 +808,7 @@ k_updagg_ordstat(OrdArgs A) {
             int64_t res = 0;
             if (bad) {
                 if (lane == 0) *A.err = UERR_ORD_CHAIN;
-            } else if (W != S.rows[slot]) {
+            } else if (W != rows) {
                 /* W <= 0 lands here too: rows > 0 for every slot taken */
                 if (lane == 0) *A.err = UERR_ORD_ROWS;
             } else {
@@ -696,6 +843,20 @@ k_updagg_ordstat(OrdArgs A) {
     }
 }
 
+__global__ void __launch_bounds__(64 * UORD_WAVES)
+k_updagg_ordstat(OrdArgs A) {
+    __shared__ OrdEnt tile_all[UORD_WAVES][UORD_TILE];
+    __shared__ long long hist_all[UORD_WAVES][256];
+    ordstat_body<false>(A, tile_all, hist_all);
+}
+
+__global__ void __launch_bounds__(64 * UORD_WAVES)
+k_updagg_ordstat_nullable(OrdArgs A) {
+    __shared__ OrdEnt tile_all[UORD_WAVES][UORD_TILE];
+    __shared__ long long hist_all[UORD_WAVES][256];
+    ordstat_body<true>(A, tile_all, hist_all);
+}
+
 struct FlushArgs {
     UStore store;
     AggSpec agg;
@@ -705,10 +866,18 @@ struct FlushArgs {
     unsigned long long *n_out;
     int64_t out_cap;
     int *err;
+    /* null semantics only */
+    uint32_t *lastv;      /* [C+1] validity mask of the last emitted row */
+    uint32_t *vmask;      /* [out_cap] validity mask per emitted row */
 };
 
-__global__ void __launch_bounds__(256)
-k_updagg_flush(FlushArgs F) {
+/* NS: a flush decision compares (validity, value) per aggregate -- NULL
+ * equals NULL and differs from every value (the value plane under a NULL is
+ * 0, so mask equality plus value equality is exactly that) -- and every
+ * emitted row carries its validity mask: bit a set = aggregate a non-NULL.
+ * Retract rows re-emit the mask that was emitted with the row they retract. */
+template <bool NS>
+__device__ __forceinline__ void flush_body(const FlushArgs &F) {
     const UStore &S = F.store;
     int na = F.agg.n_aggs;
     int lane = (int)(threadIdx.x & 63);
@@ -721,15 +890,17 @@ k_updagg_flush(FlushArgs F) {
         int64_t slot = ws + lane;
         int nr = 0;
         int64_t cur[AMD_MAX_AGGS];
+        unsigned curv = 0;
         int64_t key = 0;
         bool do_retract = false, do_append = false;
         if (slot <= (int64_t)S.C && S.epoch[slot] == F.cur_epoch &&
             (slot == (int64_t)S.C ? true : S.keys[slot] != EMPTY_KEY)) {
             key = slot == (int64_t)S.C ? EMPTY_KEY : S.keys[slot];
             long long rows = S.rows[slot];
-            if (rows > 0) ueval_slot(S, F.agg, slot, cur);
+            if (rows > 0) ueval_slot<NS>(S, F.agg, slot, cur, &curv);
             if (S.emitted[slot]) {
                 bool same = rows > 0;
+                if constexpr (NS) same = same && curv == F.lastv[slot];
                 if (same)
                     for (int a = 0; a < na; a++)
                         if (cur[a] != S.last[(size_t)slot * na + a]) {
@@ -769,6 +940,7 @@ k_updagg_flush(FlushArgs F) {
                 for (int a = 0; a < na; a++)
                     F.out[col++][r] = S.last[(size_t)slot * na + a];
                 F.out[col][r] = 1;
+                if constexpr (NS) F.vmask[r] = F.lastv[slot];
                 r++;
             }
             if (do_append) {
@@ -779,9 +951,61 @@ k_updagg_flush(FlushArgs F) {
                     S.last[(size_t)slot * na + a] = cur[a];
                 }
                 F.out[col][r] = 0;
+                if constexpr (NS) {
+                    F.vmask[r] = curv;
+                    F.lastv[slot] = curv;
+                }
                 S.emitted[slot] = 1;
             } else if (do_retract) {
                 S.emitted[slot] = 0;
+            }
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256)
+k_updagg_flush(FlushArgs F) {
+    flush_body<false>(F);
+}
+
+__global__ void __launch_bounds__(256)
+k_updagg_flush_nullable(FlushArgs F) {
+    flush_body<true>(F);
+}
+
+/* Per-row validity masks -> per-aggregate Arrow validity bitmaps.  One
+ * wave's __ballot of "row valid in aggregate a" is the little-endian 64-bit
+ * bitmap word of those 64 rows; lanes past n_rows vote 0, so the padding
+ * bits of the last word are clear.  nullcols gets bit a when aggregate a has
+ * at least one NULL row: only those bitmaps cross to the host. */
+struct PackArgs {
+    const uint32_t *vmask;
+    int64_t n_rows;
+    int32_t n_aggs;
+    uint64_t *bm[AMD_MAX_AGGS];   /* [(n_rows + 63) / 64] words each */
+    unsigned int *nullcols;
+};
+
+__global__ void __launch_bounds__(256)
+k_updagg_pack_validity(PackArgs P) {
+    int lane = (int)(threadIdx.x & 63);
+    int64_t wave_id = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / 64;
+    int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) / 64;
+    /* wave-uniform trip count: every lane reaches every __ballot */
+    for (int64_t base = wave_id * 64; base < P.n_rows; base += n_waves * 64) {
+        int64_t r = base + lane;
+        bool in = r < P.n_rows;
+        unsigned vm = in ? P.vmask[r] : 0u;
+        unsigned long long full = __ballot(in);
+        for (int a = 0; a < P.n_aggs; a++) {
+            unsigned long long w = __ballot(in && ((vm >> a) & 1));
+            if (lane == 0) {
+                P.bm[a][base >> 6] = w;
+                /* the flag saturates: look before joining the queue on
+                 * one address that every wave with a NULL would form */
+                if (w != full &&
+                    !((*(volatile unsigned int *)P.nullcols >> a) & 1))
+                    atomicOr(P.nullcols, 1u << a);
             }
         }
     }
@@ -802,6 +1026,9 @@ struct ExpireArgs {
     unsigned long long *n_out;
     int64_t out_cap;
     int *err;
+    /* null semantics only (null pointers otherwise) */
+    uint32_t *lastv;
+    uint32_t *vmask;
 };
 
 __global__ void __launch_bounds__(256)
@@ -825,6 +1052,7 @@ k_updagg_expire(ExpireArgs E) {
             for (int a = 0; a < na; a++)
                 E.out[col++][r] = S.last[(size_t)slot * na + a];
             E.out[col][r] = 1;
+            if (E.vmask) E.vmask[r] = E.lastv[slot];
         }
         S.emitted[slot] = 0;
         S.rows[slot] = 0;
@@ -835,8 +1063,9 @@ k_updagg_expire(ExpireArgs E) {
 }
 
 /* checkpoint drain which=0: scalar rows
- * [key?, rows, st words..., emitted, last...]; which=1: multiset rows
- * [key?, agg_index, value, net_count] */
+ * [key?, rows, st words..., emitted, last...] plus, under null semantics, a
+ * trailing last-emitted validity mask column (the per-aggregate n_a counts
+ * are st words); which=1: multiset rows [key?, agg_index, value, net_count] */
 struct UDrainArgs {
     UStore store;
     AggSpec agg;
@@ -845,6 +1074,7 @@ struct UDrainArgs {
     unsigned long long *n_out;
     int64_t out_cap;
     int *err;
+    const uint32_t *lastv;   /* null semantics only (null otherwise) */
 };
 
 __global__ void __launch_bounds__(256)
@@ -870,6 +1100,7 @@ k_updagg_drain(UDrainArgs D) {
             D.out[col++][r] = (int64_t)S.emitted[slot];
             for (int a = 0; a < na; a++)
                 D.out[col++][r] = S.last[(size_t)slot * na + a];
+            if (D.lastv) D.out[col++][r] = (int64_t)D.lastv[slot];
         } else {
             for (int a = 0; a < na; a++) {
                 if (D.agg.op[a] != AMD_AGG_COUNT_DISTINCT &&
@@ -903,6 +1134,7 @@ struct URestoreArgs {
     AggSpec agg;
     int32_t n_keys, which;
     int *err;
+    uint32_t *lastv;         /* null semantics only (null otherwise) */
 };
 
 __global__ void __launch_bounds__(256)
@@ -923,6 +1155,7 @@ k_updagg_restore(URestoreArgs R) {
             R.store.emitted[slot] = (uint32_t)R.cols[col++][r];
             for (int a = 0; a < na; a++)
                 R.store.last[(size_t)slot * na + a] = R.cols[col++][r];
+            if (R.lastv) R.lastv[slot] = (uint32_t)R.cols[col++][r];
         } else {
             int a = (int)R.cols[R.n_keys][r];
             chain_add(R.store, slot, a, R.cols[R.n_keys + 1][r],
@@ -952,6 +1185,15 @@ struct GpuUpdAgg {
     int has_ord;                /* config has MEDIAN / MIN_RETRACT / MAX_RETRACT */
     OrdEnt *d_arena;            /* [pool_cap] wide-chain scratch (has_ord) */
     unsigned long long *d_arena_cur;
+    /* null semantics (cfg.null_semantics == 1) only */
+    int ns;
+    uint32_t *d_lastv;          /* [C+1] last-emitted validity mask */
+    uint32_t *d_vmask;          /* [out_cap] per emitted row */
+    uint64_t *d_bm;             /* [n_aggs * bm_words] packed output bitmaps */
+    int64_t bm_words;
+    unsigned int *d_nullcols;
+    uint64_t *stg_vh[8], *stg_vd[8];   /* input bitmap staging, per value
+                                          column, stg_cap / 64 words */
     hipStream_t stream;
     char err_msg[512];
 };
@@ -996,9 +1238,16 @@ API void *arroyo_amd_updagg_create(const AmdUpdatingConfig *cfg) {
             has_ord = 1;
         }
     }
+    if (cfg->null_semantics != 0 && cfg->null_semantics != 1) {
+        snprintf(g_ua_err, sizeof g_ua_err,
+                 "invalid updagg config: null_semantics %d (0 or 1)",
+                 cfg->null_semantics);
+        return nullptr;
+    }
     GpuUpdAgg *o = new GpuUpdAgg();
     o->cfg = *cfg;
     o->has_ord = has_ord;
+    o->ns = cfg->null_semantics;
     o->agg.n_aggs = cfg->n_aggs;
     o->agg.SW = 0;
     for (int i = 0; i < cfg->n_aggs; i++) {
@@ -1006,14 +1255,7 @@ API void *arroyo_amd_updagg_create(const AmdUpdatingConfig *cfg) {
         o->agg.col[i] = cfg->agg_col[i];
         o->agg.col2[i] = cfg->agg_col2[i];
         o->agg.soff[i] = o->agg.SW;
-        int w = 2;
-        if (cfg->agg_ops[i] >= AMD_AGG_COVAR_POP &&
-            cfg->agg_ops[i] <= AMD_AGG_REGR_SXY)
-            w = 5;
-        else if (cfg->agg_ops[i] == AMD_AGG_BIT_AND ||
-                 cfg->agg_ops[i] == AMD_AGG_BIT_OR)
-            w = 32;
-        o->agg.SW += w;
+        o->agg.SW += ua_width(cfg->agg_ops[i], o->ns);
     }
     if (o->agg.SW > UAGG_MAX_SW) {
         snprintf(g_ua_err, sizeof g_ua_err,
@@ -1027,7 +1269,8 @@ API void *arroyo_amd_updagg_create(const AmdUpdatingConfig *cfg) {
     o->out_cap = 1ll << (cfg->log2_out_cap ? cfg->log2_out_cap : 20);
     o->n_in_cols = cfg->n_keys + cfg->n_value_cols + 1;
     o->out_cols = cfg->n_keys + cfg->n_aggs + 1;
-    o->drain0_cols = cfg->n_keys + 1 + o->agg.SW + 1 + cfg->n_aggs;
+    o->drain0_cols = cfg->n_keys + 1 + o->agg.SW + 1 + cfg->n_aggs +
+                     (o->ns ? 1 : 0);
     o->drain1_cols = cfg->n_keys + 3;
     o->cur_epoch = 1;
     if (hipSetDevice(cfg->device) != hipSuccess) {
@@ -1072,6 +1315,14 @@ API void *arroyo_amd_updagg_create(const AmdUpdatingConfig *cfg) {
         UALLOC(o->d_out[i], (size_t)o->out_cap * 8);
     UALLOC(o->d_n_out, 8);
     UALLOC(o->d_err, 4);
+    if (o->ns) {
+        o->bm_words = o->out_cap / 64 + 1;
+        UALLOC(o->d_lastv, C1 * 4);
+        UALLOC(o->d_vmask, (size_t)o->out_cap * 4);
+        UALLOC(o->d_bm, na * (size_t)o->bm_words * 8);
+        UALLOC(o->d_nullcols, 4);
+        hipMemset(o->d_lastv, 0, C1 * 4);
+    }
 #undef UALLOC
     hipMemset(o->store.keys, 0xFF, C1 * 8);
     hipMemset(o->store.epoch, 0, C1 * 4);
@@ -1092,6 +1343,16 @@ API void *arroyo_amd_updagg_create(const AmdUpdatingConfig *cfg) {
             hipMalloc((void **)&o->stg_d[c], (size_t)o->stg_cap * 8) !=
                 hipSuccess) {
             snprintf(g_ua_err, sizeof g_ua_err, "updagg staging alloc failed");
+            delete o;
+            return nullptr;
+        }
+    }
+    for (int v = 0; o->ns && v < cfg->n_value_cols; v++) {
+        size_t bytes = (size_t)(o->stg_cap / 64) * 8;
+        if (hipHostMalloc((void **)&o->stg_vh[v], bytes) != hipSuccess ||
+            hipMalloc((void **)&o->stg_vd[v], bytes) != hipSuccess) {
+            snprintf(g_ua_err, sizeof g_ua_err,
+                     "updagg validity staging alloc failed");
             delete o;
             return nullptr;
         }
@@ -1130,6 +1391,117 @@ static int ua_grid(int64_t want_threads) {
     return (int)(want > 2048 ? 2048 : (want < 1 ? 1 : want));
 }
 
+static void ua_fill_update_args(GpuUpdAgg *o, UpdateArgs *A, int64_t n_rows) {
+    A->n_keys = o->cfg.n_keys;
+    A->n_vals = o->cfg.n_value_cols;
+    A->n_rows = n_rows;
+    A->store = o->store;
+    A->agg = o->agg;
+    A->cur_epoch = o->cur_epoch;
+    A->err = o->d_err;
+}
+
+/* shared argument checks of the nullable entry points */
+static int ua_check_nullable(GpuUpdAgg *o, const uint8_t *const *validity,
+                             int32_t n_cols) {
+    if (!o->ns) {
+        snprintf(o->err_msg, sizeof o->err_msg,
+                 "process_batch_nullable needs a handle created with "
+                 "null_semantics = 1");
+        return 1;
+    }
+    if (n_cols != o->n_in_cols) {
+        snprintf(o->err_msg, sizeof o->err_msg, "expected %d cols, got %d",
+                 o->n_in_cols, n_cols);
+        return 1;
+    }
+    if (validity) {
+        if (o->cfg.n_keys && validity[0]) {
+            snprintf(o->err_msg, sizeof o->err_msg,
+                     "validity bitmap on the key column: NULL group keys "
+                     "are not supported");
+            return 1;
+        }
+        if (validity[n_cols - 1]) {
+            snprintf(o->err_msg, sizeof o->err_msg,
+                     "validity bitmap on the is_retract column: it is "
+                     "non-nullable");
+            return 1;
+        }
+    }
+    return 0;
+}
+
+/* host ingest; validity == nullptr (or an entry of it) = all valid.  Chunks
+ * are stg_cap = 2^20 rows, so a chunk starts on a bitmap byte boundary. */
+static int ua_process_host(GpuUpdAgg *o, const int64_t *const *cols,
+                           const uint8_t *const *validity, int32_t n_cols,
+                           int64_t n_rows) {
+    int64_t done = 0;
+    while (done < n_rows) {
+        int64_t take = n_rows - done;
+        if (take > o->stg_cap) take = o->stg_cap;
+        UpdateArgsN N = {};
+        UpdateArgs &A = N.A;
+        for (int c = 0; c < n_cols; c++) {
+            memcpy(o->stg_h[c], cols[c] + done, (size_t)take * 8);
+            UHIP(o, hipMemcpyAsync(o->stg_d[c], o->stg_h[c],
+                                   (size_t)take * 8, hipMemcpyHostToDevice,
+                                   o->stream));
+            A.cols[c] = o->stg_d[c];
+        }
+        for (int v = 0; validity && v < o->cfg.n_value_cols; v++) {
+            const uint8_t *bm = validity[o->cfg.n_keys + v];
+            if (!bm) continue;
+            size_t nbytes = (size_t)((take + 7) / 8);
+            size_t nwords = (size_t)((take + 63) / 64);
+            o->stg_vh[v][nwords - 1] = 0;   /* pad the last word */
+            memcpy(o->stg_vh[v], bm + done / 8, nbytes);
+            UHIP(o, hipMemcpyAsync(o->stg_vd[v], o->stg_vh[v], nwords * 8,
+                                   hipMemcpyHostToDevice, o->stream));
+            N.valid[v] = o->stg_vd[v];
+        }
+        ua_fill_update_args(o, &A, take);
+        if (o->ns)
+            hipLaunchKernelGGL(k_updagg_update_nullable, dim3(ua_grid(take)),
+                               dim3(256), 0, o->stream, N);
+        else
+            hipLaunchKernelGGL(k_updagg_update, dim3(ua_grid(take)),
+                               dim3(256), 0, o->stream, A);
+        UHIP(o, hipGetLastError());
+        UHIP(o, hipStreamSynchronize(o->stream));
+        done += take;
+    }
+    return 0;
+}
+
+static int ua_process_device(GpuUpdAgg *o, const int64_t *const *dcols,
+                             const uint8_t *const *dvalidity, int32_t n_cols,
+                             int64_t n_rows) {
+    UpdateArgsN N = {};
+    UpdateArgs &A = N.A;
+    for (int c = 0; c < n_cols; c++) A.cols[c] = dcols[c];
+    for (int v = 0; dvalidity && v < o->cfg.n_value_cols; v++) {
+        const uint8_t *bm = dvalidity[o->cfg.n_keys + v];
+        if ((uintptr_t)bm & 7) {
+            snprintf(o->err_msg, sizeof o->err_msg,
+                     "device validity bitmap of column %d is not 8-byte "
+                     "aligned", o->cfg.n_keys + v);
+            return 1;
+        }
+        N.valid[v] = (const uint64_t *)bm;
+    }
+    ua_fill_update_args(o, &A, n_rows);
+    if (o->ns)
+        hipLaunchKernelGGL(k_updagg_update_nullable, dim3(ua_grid(n_rows)),
+                           dim3(256), 0, o->stream, N);
+    else
+        hipLaunchKernelGGL(k_updagg_update, dim3(ua_grid(n_rows)), dim3(256),
+                           0, o->stream, A);
+    UHIP(o, hipGetLastError());
+    return 0;
+}
+
 API int arroyo_amd_updagg_process_batch(void *h, const int64_t *const *cols,
                                         int32_t n_cols, int64_t n_rows) {
     GpuUpdAgg *o = (GpuUpdAgg *)h;
@@ -1138,32 +1510,7 @@ API int arroyo_amd_updagg_process_batch(void *h, const int64_t *const *cols,
                  o->n_in_cols, n_cols);
         return 1;
     }
-    int64_t done = 0;
-    while (done < n_rows) {
-        int64_t take = n_rows - done;
-        if (take > o->stg_cap) take = o->stg_cap;
-        UpdateArgs A = {};
-        for (int c = 0; c < n_cols; c++) {
-            memcpy(o->stg_h[c], cols[c] + done, (size_t)take * 8);
-            UHIP(o, hipMemcpyAsync(o->stg_d[c], o->stg_h[c],
-                                   (size_t)take * 8, hipMemcpyHostToDevice,
-                                   o->stream));
-            A.cols[c] = o->stg_d[c];
-        }
-        A.n_keys = o->cfg.n_keys;
-        A.n_vals = o->cfg.n_value_cols;
-        A.n_rows = take;
-        A.store = o->store;
-        A.agg = o->agg;
-        A.cur_epoch = o->cur_epoch;
-        A.err = o->d_err;
-        hipLaunchKernelGGL(k_updagg_update, dim3(ua_grid(take)), dim3(256),
-                           0, o->stream, A);
-        UHIP(o, hipGetLastError());
-        UHIP(o, hipStreamSynchronize(o->stream));
-        done += take;
-    }
-    return 0;
+    return ua_process_host(o, cols, nullptr, n_cols, n_rows);
 }
 
 API int arroyo_amd_updagg_process_batch_device(void *h,
@@ -1176,18 +1523,69 @@ API int arroyo_amd_updagg_process_batch_device(void *h,
                  o->n_in_cols, n_cols);
         return 1;
     }
-    UpdateArgs A = {};
-    for (int c = 0; c < n_cols; c++) A.cols[c] = dcols[c];
-    A.n_keys = o->cfg.n_keys;
-    A.n_vals = o->cfg.n_value_cols;
-    A.n_rows = n_rows;
-    A.store = o->store;
-    A.agg = o->agg;
-    A.cur_epoch = o->cur_epoch;
-    A.err = o->d_err;
-    hipLaunchKernelGGL(k_updagg_update, dim3(ua_grid(n_rows)), dim3(256), 0,
-                       o->stream, A);
+    return ua_process_device(o, dcols, nullptr, n_cols, n_rows);
+}
+
+API int arroyo_amd_updagg_process_batch_nullable(
+    void *h, const int64_t *const *cols, const uint8_t *const *validity,
+    int32_t n_cols, int64_t n_rows) {
+    GpuUpdAgg *o = (GpuUpdAgg *)h;
+    if (ua_check_nullable(o, validity, n_cols)) return 1;
+    return ua_process_host(o, cols, validity, n_cols, n_rows);
+}
+
+API int arroyo_amd_updagg_process_batch_nullable_device(
+    void *h, const int64_t *const *dcols, const uint8_t *const *dvalidity,
+    int32_t n_cols, int64_t n_rows) {
+    GpuUpdAgg *o = (GpuUpdAgg *)h;
+    if (ua_check_nullable(o, dvalidity, n_cols)) return 1;
+    return ua_process_device(o, dcols, dvalidity, n_cols, n_rows);
+}
+
+/* null semantics: pack the emitted rows' validity masks (d_vmask) into
+ * per-aggregate Arrow bitmaps on the device and attach to `out` the bitmaps
+ * of the aggregate columns that hold at least one NULL.  Key and is_retract
+ * columns, and fully valid aggregate columns, keep a NULL pointer.  A
+ * failed allocation is an error, never an "all valid". */
+static int ua_fill_validity(GpuUpdAgg *o, AmdOutBatch *out) {
+    if (!o->ns) return 0;
+    int64_t n = out->n_rows;
+    out->validity = (uint8_t **)calloc(o->out_cols, sizeof(uint8_t *));
+    if (!out->validity) {
+        snprintf(o->err_msg, sizeof o->err_msg,
+                 "validity bitmap table allocation failed");
+        return 1;
+    }
+    if (n == 0) return 0;
+    int na = o->cfg.n_aggs;
+    UHIP(o, hipMemsetAsync(o->d_nullcols, 0, 4, o->stream));
+    PackArgs P = {};
+    P.vmask = o->d_vmask;
+    P.n_rows = n;
+    P.n_aggs = na;
+    for (int a = 0; a < na; a++) P.bm[a] = o->d_bm + (size_t)a * o->bm_words;
+    P.nullcols = o->d_nullcols;
+    hipLaunchKernelGGL(k_updagg_pack_validity, dim3(ua_grid(n)), dim3(256),
+                       0, o->stream, P);
     UHIP(o, hipGetLastError());
+    unsigned int nullcols = 0;
+    UHIP(o, hipMemcpyAsync(&nullcols, o->d_nullcols, 4,
+                           hipMemcpyDeviceToHost, o->stream));
+    UHIP(o, hipStreamSynchronize(o->stream));
+    size_t nbytes = (size_t)((n + 7) / 8);
+    for (int a = 0; a < na; a++) {
+        if (!((nullcols >> a) & 1)) continue;
+        uint8_t *bm = (uint8_t *)malloc(nbytes);
+        if (!bm) {
+            snprintf(o->err_msg, sizeof o->err_msg,
+                     "validity bitmap allocation failed (%zu bytes)", nbytes);
+            return 1;
+        }
+        out->validity[o->cfg.n_keys + a] = bm;
+        UHIP(o, hipMemcpyAsync(bm, P.bm[a], nbytes, hipMemcpyDeviceToHost,
+                               o->stream));
+    }
+    UHIP(o, hipStreamSynchronize(o->stream));
     return 0;
 }
 
@@ -1207,8 +1605,13 @@ API int arroyo_amd_updagg_flush(void *h, AmdOutBatch *out) {
         R.arena_cap = o->store.pool_cap;
         R.err = o->d_err;
         int64_t waves = ((int64_t)o->store.C + 1 + 7) / 8;
-        hipLaunchKernelGGL(k_updagg_ordstat, dim3(ua_grid(waves * 64)),
-                           dim3(64 * UORD_WAVES), 0, o->stream, R);
+        if (o->ns)
+            hipLaunchKernelGGL(k_updagg_ordstat_nullable,
+                               dim3(ua_grid(waves * 64)),
+                               dim3(64 * UORD_WAVES), 0, o->stream, R);
+        else
+            hipLaunchKernelGGL(k_updagg_ordstat, dim3(ua_grid(waves * 64)),
+                               dim3(64 * UORD_WAVES), 0, o->stream, R);
         UHIP(o, hipGetLastError());
     }
     FlushArgs F = {};
@@ -1220,9 +1623,16 @@ API int arroyo_amd_updagg_flush(void *h, AmdOutBatch *out) {
     F.n_out = o->d_n_out;
     F.out_cap = o->out_cap;
     F.err = o->d_err;
-    hipLaunchKernelGGL(k_updagg_flush,
-                       dim3(ua_grid((int64_t)o->store.C + 1)), dim3(256), 0,
-                       o->stream, F);
+    F.lastv = o->d_lastv;
+    F.vmask = o->d_vmask;
+    if (o->ns)
+        hipLaunchKernelGGL(k_updagg_flush_nullable,
+                           dim3(ua_grid((int64_t)o->store.C + 1)), dim3(256),
+                           0, o->stream, F);
+    else
+        hipLaunchKernelGGL(k_updagg_flush,
+                           dim3(ua_grid((int64_t)o->store.C + 1)), dim3(256),
+                           0, o->stream, F);
     UHIP(o, hipGetLastError());
     unsigned long long n = 0;
     UHIP(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
@@ -1252,6 +1662,7 @@ API int arroyo_amd_updagg_flush(void *h, AmdOutBatch *out) {
                                        o->stream));
         }
         UHIP(o, hipStreamSynchronize(o->stream));
+        if (ua_fill_validity(o, out)) return 1;
     }
     return 0;
 }
@@ -1271,6 +1682,8 @@ API int arroyo_amd_updagg_expire(void *h, int64_t idle_flushes,
     E.n_out = o->d_n_out;
     E.out_cap = o->out_cap;
     E.err = o->d_err;
+    E.lastv = o->d_lastv;
+    E.vmask = o->d_vmask;
     hipLaunchKernelGGL(k_updagg_expire,
                        dim3(ua_grid((int64_t)o->store.C + 1)), dim3(256), 0,
                        o->stream, E);
@@ -1294,6 +1707,7 @@ API int arroyo_amd_updagg_expire(void *h, int64_t idle_flushes,
                                        o->stream));
         }
         UHIP(o, hipStreamSynchronize(o->stream));
+        if (ua_fill_validity(o, out)) return 1;
     }
     return 0;
 }
@@ -1313,6 +1727,7 @@ API int arroyo_amd_updagg_checkpoint_drain(void *h, int32_t which,
     D.n_out = o->d_n_out;
     D.out_cap = o->out_cap;
     D.err = o->d_err;
+    D.lastv = o->d_lastv;
     hipLaunchKernelGGL(k_updagg_drain,
                        dim3(ua_grid((int64_t)o->store.C + 1)), dim3(256), 0,
                        o->stream, D);
@@ -1370,6 +1785,7 @@ API int arroyo_amd_updagg_restore(void *h, int32_t which,
         R.n_keys = o->cfg.n_keys;
         R.which = which;
         R.err = o->d_err;
+        R.lastv = o->d_lastv;
         hipLaunchKernelGGL(k_updagg_restore, dim3(ua_grid(take)), dim3(256),
                            0, o->stream, R);
         UHIP(o, hipGetLastError());
@@ -1407,6 +1823,16 @@ API void arroyo_amd_updagg_destroy(void *h) {
     for (int c = 0; c < o->n_in_cols; c++) {
         hipHostFree(o->stg_h[c]);
         hipFree(o->stg_d[c]);
+    }
+    if (o->ns) {
+        hipFree(o->d_lastv);
+        hipFree(o->d_vmask);
+        hipFree(o->d_bm);
+        hipFree(o->d_nullcols);
+        for (int v = 0; v < o->cfg.n_value_cols; v++) {
+            hipHostFree(o->stg_vh[v]);
+            hipFree(o->stg_vd[v]);
+        }
     }
     hipStreamDestroy(o->stream);
     delete o;

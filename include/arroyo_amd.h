@@ -290,6 +290,29 @@ int arroyo_amd_updagg_process_batch(void *h, const int64_t *const *cols,
 int arroyo_amd_updagg_process_batch_device(void *h,
                                            const int64_t *const *dcols,
                                            int32_t n_cols, int64_t n_rows);
+/* Nullable ingest (handles created with null_semantics = 1 only; a loud
+ * error otherwise).  `validity` may be NULL (everything valid) and
+ * validity[c] may be NULL (column c all valid); otherwise validity[c] is an
+ * Arrow validity bitmap -- LSB bit order, bit offset 0, (n_rows + 7) / 8
+ * bytes, the layout of AmdOutBatch.validity.  A bitmap on the key column or
+ * on is_retract is an error (NULL group keys are not supported).  The host
+ * surface stages the data and makes no alignment or padding demand.  The
+ * device surface reads the bitmaps in place as 64-bit words: each
+ * dvalidity[c] must be 8-byte aligned and its buffer padded to a multiple
+ * of 8 bytes (Arrow buffers are).  The plain process_batch* calls stay
+ * legal on a null_semantics = 1 handle and mean "all valid".  Under
+ * null_semantics = 1, flush and expire set out->validity: NULL pointers for
+ * the key and is_retract columns and for an aggregate column whose emitted
+ * rows are all valid, a bitmap otherwise (freed by arroyo_amd_free_out);
+ * checkpoint_drain(0) rows gain one trailing column, the validity mask of
+ * the key's last emitted row (bit a = aggregate a non-NULL). */
+int arroyo_amd_updagg_process_batch_nullable(void *h,
+                                             const int64_t *const *cols,
+                                             const uint8_t *const *validity,
+                                             int32_t n_cols, int64_t n_rows);
+int arroyo_amd_updagg_process_batch_nullable_device(
+    void *h, const int64_t *const *dcols, const uint8_t *const *dvalidity,
+    int32_t n_cols, int64_t n_rows);
 int arroyo_amd_updagg_flush(void *h, AmdOutBatch *out);
 /* TTL eviction of keys idle for more than `idle_flushes` flush epochs
  * (the reference's UpdatingCache::time_out, wall-clock there); emits the

@@ -38,9 +38,12 @@ enum AmdAggOp {
                                    distinct values under append+retract */
     /* round 2, updating aggregate only (every_aggregate.sql coverage):
      * retractable co-moment states.  n is the key's live row count (the
-     * aggregated column is non-null in this ABI), state = (sum(x) f64,
-     * sum(x^2) f64); sample variants emit NaN when n < 2 (the reference
-     * emits SQL NULL there). */
+     * aggregated column is non-null unless the updating aggregate runs with
+     * AmdUpdatingConfig.null_semantics = 1; then n is the count of live
+     * rows whose argument is non-null), state = (sum(x) f64, sum(x^2) f64);
+     * sample variants emit NaN when n < 2 (the reference emits SQL NULL
+     * there, and so does null_semantics = 1, through the output validity
+     * bitmap). */
     AMD_AGG_STDDEV = 6,
     AMD_AGG_STDDEV_POP = 7,
     AMD_AGG_VAR = 8,
@@ -49,7 +52,9 @@ enum AmdAggOp {
     /* two-argument co-moment family (updating aggregate only): state =
      * (sum y, sum x, sum xy, sum y^2, sum x^2) f64; the FIRST argument
      * (SQL's Y) is agg_col, the second (X) agg_col2.  Sample variants and
-     * zero-variance cases emit NaN where the reference emits SQL NULL. */
+     * zero-variance cases emit NaN where the reference emits SQL NULL
+     * (a NULL in the validity bitmap under null_semantics = 1, where a row
+     * contributes only when both arguments are non-null). */
     AMD_AGG_COVAR_POP = 11,
     AMD_AGG_COVAR_SAMP = 12,
     AMD_AGG_CORR = 13,
@@ -248,6 +253,23 @@ typedef struct {
     uint32_t log2_out_cap;
     int32_t  device;
     int32_t  emit_to_host;
+    int32_t  null_semantics;    /* 0: non-nullable value columns, NaN where
+                                   the reference emits SQL NULL, no output
+                                   validity (the contract above, unchanged).
+                                   1: SQL NULL semantics -- value columns may
+                                   carry Arrow validity bitmaps
+                                   (updagg_process_batch_nullable), an
+                                   aggregate skips rows whose argument is
+                                   NULL (either argument for the co-moment
+                                   family) and counts the remaining live
+                                   rows n_a; COUNT / COUNT DISTINCT /
+                                   REGR_COUNT are never NULL, every other
+                                   aggregate is NULL when n_a == 0 or its
+                                   result is undefined (sample variants at
+                                   n_a < 2, zero-variance CORR / REGR_SLOPE
+                                   / REGR_INTERCEPT / REGR_R2); flush and
+                                   expire set AmdOutBatch.validity and the
+                                   value under a NULL is 0 */
 } AmdUpdatingConfig;
 
 /* SQL window-function (ROW_NUMBER) configuration.  Mirrors

@@ -142,6 +142,80 @@ def bench_updagg_device():
           f"{dt*1e6/batches:.0f} us per 1M-row batch)")
 
 
+def updagg_device_rate(null_semantics, null_frac=0.0, min_seconds=1.0,
+                       windows=3):
+    """The updagg_device shape (COUNT+SUM, 2M keys, 1M-row device-resident
+    batches, a flush every 8), warmed up with 48 batches and then timed over
+    `windows` windows of at least `min_seconds` each.  null_semantics=False
+    drives process_batch_device, True process_batch_nullable_device with
+    `null_frac` of the value column NULL.  Returns us per 1M-row batch, one
+    figure per window (host clock around a window that ends in a flush, i.e.
+    a stream synchronise)."""
+    import torch
+    from arroyo_amd import cabi, gpu
+    rng = np.random.default_rng(4)
+    n = 1 << 20
+    dev = torch.device("cuda", 0)
+    op = gpu.make_updagg_op(cabi.make_updagg_config(
+        [(cabi.COUNT, -1), (cabi.SUM, 0)], n_keys=1, n_value_cols=1,
+        log2_capacity=22, log2_out_cap=24, null_semantics=null_semantics))
+    key = torch.from_numpy(
+        rng.integers(0, 1 << 21, size=n * 2).astype(np.int64)).to(dev)
+    val = torch.from_numpy(
+        rng.integers(0, 1000, size=n * 2).astype(np.int64)).to(dev)
+    ret = torch.zeros(n * 2, dtype=torch.int64, device=dev)
+    # n is a multiple of 64, so the second half's bitmap is 8-byte aligned
+    bm = torch.from_numpy(
+        cabi.pack_validity(rng.random(n * 2) >= null_frac)).to(dev)
+    torch.cuda.synchronize()
+
+    def run(batches):
+        for i in range(batches):
+            lo = (i % 2) * n
+            ptrs = [key.data_ptr() + lo * 8, val.data_ptr() + lo * 8,
+                    ret.data_ptr() + lo * 8]
+            if null_semantics:
+                op.process_batch_nullable_device(
+                    ptrs, [None, bm.data_ptr() + lo // 8, None], n)
+            else:
+                op.process_batch_device(ptrs, n)
+            if i % 8 == 7:
+                op.flush()
+
+    run(48)
+    out = []
+    for _ in range(windows):
+        done = 0
+        t0 = time.perf_counter()
+        while True:
+            run(48)
+            done += 48
+            dt = time.perf_counter() - t0
+            if dt >= min_seconds:
+                break
+        out.append(dt * 1e6 / done)
+    op.close()
+    return out
+
+
+def bench_updagg_nullable_device(which=("plain", "0", "10")):
+    """Nullable device-resident ingest against the non-nullable path at the
+    same commit, same shape and same method.  which: "plain" = the
+    null_semantics=0 path, "0" / "10" = nullable with that % of NULLs."""
+    import json
+    legs = {"plain": ("updagg_device (null_semantics=0)", False, 0.0),
+            "0": ("updagg_nullable_device 0% NULL", True, 0.0),
+            "10": ("updagg_nullable_device 10% NULL", True, 0.10)}
+    for name, ns, frac in (legs[w] for w in which):
+        us = updagg_device_rate(ns, frac)
+        print(f"{name}: {np.median(us):.0f} us per 1M-row batch "
+              f"({(1 << 20) / np.median(us) / 1e3:.3f} Grows/s; windows "
+              f"{', '.join(f'{u:.0f}' for u in us)} us)")
+        print(json.dumps({"leg": "updagg_nullable_device", "name": name,
+                          "null_semantics": int(ns), "null_frac": frac,
+                          "us_per_1M_windows": us}))
+
+
 def bench_ordered(which=("A", "B"), reps=10, warmup=2):
     """Updating aggregate with per-key value multisets: 2^16 keys x ~100
     distinct values per key.  Config A = COUNT + COUNT DISTINCT (no
@@ -202,7 +276,9 @@ def bench_ordered(which=("A", "B"), reps=10, warmup=2):
 
 LEGS = {"expjoin": bench_expjoin, "updagg": bench_updagg,
         "expjoin_device": bench_expjoin_device,
-        "updagg_device": bench_updagg_device, "ordered": bench_ordered}
+        "updagg_device": bench_updagg_device,
+        "updagg_nullable_device": bench_updagg_nullable_device,
+        "ordered": bench_ordered}
 
 
 if __name__ == "__main__":
