@@ -1252,3 +1252,198 @@ class MapOp:
             self.close()
         except Exception:
             pass
+
+
+# ---- device string-key dictionary (arroyo_amd_strkey_*) -------------------
+
+class AmdStrKeyConfig(ctypes.Structure):
+    _fields_ = [
+        ("device", ctypes.c_int32),
+        ("log2_capacity", ctypes.c_int32),
+        ("arena_bytes", ctypes.c_int64),
+        ("hash_bits", ctypes.c_int32),
+    ]
+
+
+class AmdStrBatch(ctypes.Structure):
+    _fields_ = [
+        ("n_rows", ctypes.c_int64),
+        ("ids", ctypes.POINTER(ctypes.c_int64)),
+        ("offsets", ctypes.POINTER(ctypes.c_int32)),
+        ("data", ctypes.POINTER(ctypes.c_uint8)),
+    ]
+
+
+def make_strkey_config(log2_capacity=16, arena_bytes=1 << 24, hash_bits=0,
+                       device=0):
+    cfg = AmdStrKeyConfig()
+    cfg.device = device
+    cfg.log2_capacity = log2_capacity
+    cfg.arena_bytes = arena_bytes
+    cfg.hash_bits = hash_bits
+    return cfg
+
+
+def strings_to_arrow(strings):
+    """list[bytes | str] -> (int32 offsets [n + 1], uint8 data): the two
+    buffers of an Arrow Utf8 array.  str items are encoded as UTF-8."""
+    raw = [s.encode("utf-8") if isinstance(s, str) else bytes(s)
+           for s in strings]
+    lens = np.fromiter((len(b) for b in raw), dtype=np.int64, count=len(raw))
+    offsets = np.zeros(len(raw) + 1, dtype=np.int64)
+    np.cumsum(lens, out=offsets[1:])
+    if offsets[-1] > np.iinfo(np.int32).max:
+        raise ValueError("strings exceed the int32 offset range of Utf8")
+    data = np.frombuffer(b"".join(raw), dtype=np.uint8).copy()
+    return offsets.astype(np.int32), data
+
+
+def arrow_to_strings(offsets, data):
+    """(offsets, data) -> list[bytes]; honours a non-zero offsets[0]."""
+    buf = np.ascontiguousarray(data, dtype=np.uint8).tobytes()
+    off = [int(o) for o in offsets]
+    return [buf[off[i]:off[i + 1]] for i in range(len(off) - 1)]
+
+
+def _strbatch_to_numpy(out):
+    n = int(out.n_rows)
+    ids = np.ctypeslib.as_array(out.ids, shape=(n,)).copy() if n else \
+        np.zeros(0, dtype=np.int64)
+    offsets = np.ctypeslib.as_array(out.offsets, shape=(n + 1,)).copy()
+    total = int(offsets[-1])
+    data = np.ctypeslib.as_array(out.data, shape=(total,)).copy() if total \
+        else np.zeros(0, dtype=np.uint8)
+    return ids, offsets, data
+
+
+class StrKeyDict:
+    """Device-resident string interner behind the C ABI: Arrow Utf8 key
+    columns in, stable non-negative int64 ids out (and back).  Share one
+    instance between every operator that must agree on the ids."""
+
+    def __init__(self, lib, prefix, cfg):
+        p = prefix + "strkey_"
+        g = lambda n: getattr(lib, p + n)
+        vp, i64 = ctypes.c_void_p, ctypes.c_int64
+        fn = {}
+        fn["create"] = g("create")
+        fn["create"].restype = vp
+        fn["create"].argtypes = [ctypes.POINTER(AmdStrKeyConfig)]
+        for name, args in (
+                ("encode", [vp, vp, vp, i64, vp, vp]),
+                ("encode_device", [vp, vp, vp, i64, vp, vp]),
+                ("decode", [vp, vp, i64, ctypes.POINTER(AmdStrBatch)]),
+                ("count", [vp, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
+                ("checkpoint_drain", [vp, ctypes.POINTER(AmdStrBatch)]),
+                ("restore", [vp, vp, vp, vp, i64]),
+                ("profile", [vp, ctypes.c_int,
+                             ctypes.POINTER(ctypes.c_double)])):
+            fn[name] = g(name)
+            fn[name].restype = ctypes.c_int
+            fn[name].argtypes = args
+        fn["free_out"] = g("free_out")
+        fn["free_out"].restype = None
+        fn["free_out"].argtypes = [ctypes.POINTER(AmdStrBatch)]
+        fn["destroy"] = g("destroy")
+        fn["destroy"].restype = None
+        fn["destroy"].argtypes = [vp]
+        fn["last_error"] = g("last_error")
+        fn["last_error"].restype = ctypes.c_char_p
+        fn["last_error"].argtypes = [vp]
+        self._fn = fn
+        self.cfg = cfg
+        self._h = fn["create"](ctypes.byref(cfg))
+        if not self._h:
+            raise RuntimeError(
+                f"{p}create failed: {fn['last_error'](None).decode()}")
+
+    def _check(self, rc):
+        if rc != 0:
+            raise RuntimeError(self._fn["last_error"](self._h).decode())
+
+    @staticmethod
+    def _arrow(offsets, data):
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        if len(offsets) < 1:
+            raise ValueError("offsets needs n_rows + 1 entries")
+        return offsets, data
+
+    def encode(self, offsets, data, with_hashes=False):
+        """Host Arrow buffers -> int64 ids (and uint64 content hashes when
+        with_hashes)."""
+        offsets, data = self._arrow(offsets, data)
+        n = len(offsets) - 1
+        ids = np.empty(n, dtype=np.int64)
+        hashes = np.empty(n, dtype=np.uint64) if with_hashes else None
+        self._check(self._fn["encode"](
+            self._h, offsets.ctypes.data, data.ctypes.data, n,
+            ids.ctypes.data, hashes.ctypes.data if with_hashes else None))
+        return (ids, hashes) if with_hashes else ids
+
+    def encode_device(self, d_offsets, d_data, n, d_ids, d_hashes=None):
+        """Device pointers (ints) in, ids (and hashes) written on device;
+        synchronised on return."""
+        self._check(self._fn["encode_device"](
+            self._h, d_offsets, d_data, n, d_ids, d_hashes))
+
+    def decode(self, ids):
+        """int64 ids -> (int32 offsets, uint8 data)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        out = AmdStrBatch()
+        self._check(self._fn["decode"](self._h, ids.ctypes.data, len(ids),
+                                       ctypes.byref(out)))
+        _, offsets, data = _strbatch_to_numpy(out)
+        self._fn["free_out"](ctypes.byref(out))
+        return offsets, data
+
+    def drain(self):
+        """Checkpoint: every interned string -> (ids, offsets, data)."""
+        out = AmdStrBatch()
+        self._check(self._fn["checkpoint_drain"](self._h, ctypes.byref(out)))
+        res = _strbatch_to_numpy(out)
+        self._fn["free_out"](ctypes.byref(out))
+        return res
+
+    def restore(self, ids, offsets, data):
+        """Load a drain() into this (empty) handle; every string keeps its
+        id."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        offsets, data = self._arrow(offsets, data)
+        if len(ids) != len(offsets) - 1:
+            raise ValueError("ids and offsets disagree on the row count")
+        self._check(self._fn["restore"](
+            self._h, ids.ctypes.data, offsets.ctypes.data, data.ctypes.data,
+            len(ids)))
+
+    def count(self):
+        """Number of interned strings."""
+        n = ctypes.c_int64(0)
+        self._check(self._fn["count"](self._h, ctypes.byref(n), None))
+        return int(n.value)
+
+    def profile(self, enable=None):
+        """Switch per-encode timing of the lookup kernel on/off (None leaves
+        it); returns the kernel milliseconds of the last timed encode."""
+        ms = ctypes.c_double(0.0)
+        self._check(self._fn["profile"](
+            self._h, -1 if enable is None else int(bool(enable)),
+            ctypes.byref(ms)))
+        return ms.value
+
+    def arena_used(self):
+        """Arena bytes in use (each string rounded up to 8 bytes)."""
+        used = ctypes.c_int64(0)
+        self._check(self._fn["count"](self._h, None, ctypes.byref(used)))
+        return int(used.value)
+
+    def close(self):
+        if self._h:
+            self._fn["destroy"](self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

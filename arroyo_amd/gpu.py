@@ -16,7 +16,7 @@ _DIR = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_DIR, "libarroyo_amd.so")
 _SRCS = [os.path.join(_DIR, "csrc", f)
          for f in ("arroyo_amd.hip", "session.hip", "expjoin.hip",
-                   "updagg.hip", "windowfn.hip", "mapop.hip")]
+                   "updagg.hip", "windowfn.hip", "mapop.hip", "strkey.hip")]
 
 _lib = None
 
@@ -185,3 +185,8 @@ def make_windowfn_op(cfg):
 def make_map_op(cfg):
     from arroyo_amd.cabi import MapOp
     return MapOp(lib(), "arroyo_amd_", cfg)
+
+
+def make_strkey(cfg):
+    from arroyo_amd.cabi import StrKeyDict
+    return StrKeyDict(lib(), "arroyo_amd_", cfg)

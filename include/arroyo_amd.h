@@ -375,6 +375,83 @@ int arroyo_amd_map_process_batch_device(void *h, const int64_t *const *dcols,
 void arroyo_amd_map_destroy(void *h);
 const char *arroyo_amd_map_last_error(void *h);
 
+/* ---- device string-key dictionary --------------------------------------
+ * The reference keys state on arbitrary Arrow types by row-encoding the key
+ * tuple (crates/arroyo-state/src/tables/expiring_time_key_map.rs:1008-1049);
+ * SQL such as `GROUP BY event_type` keys on Utf8.  This family interns an
+ * Arrow Utf8 array (int32 offsets + byte buffer) on device: every string
+ * maps to an opaque, stable, non-negative i64 id that any operator above
+ * accepts as a key column, and ids map back to strings at emission.  It has
+ * no window or watermark logic; it sits in front of and behind the other
+ * operators.  One handle is shared by every operator that must agree on the
+ * ids: both sides of a join keyed on the same column, or a map -> window ->
+ * window-function chain.
+ *
+ *   strkey_encode / _device   <-> the key row-encoding ahead of process_batch
+ *   strkey_decode             <-> rebuilding the key column of an emission
+ *   strkey_checkpoint_drain / strkey_restore
+ *                             <-> part of the keyed operators' checkpoint:
+ *                                 their drained state refers to these ids
+ *
+ * Offsets: n_rows + 1 entries; row r is data[offsets[r] .. offsets[r+1]);
+ * offsets[0] may be non-zero (a sliced array).  No byte of `data` outside
+ * [offsets[0], offsets[n_rows]) is ever read.  A negative or decreasing
+ * offset is an error, detected on the device before any byte is read.
+ *
+ * Ids: equal byte strings get equal ids and different byte strings get
+ * different ids, for the life of the handle and across batches; only a full
+ * length-and-bytes compare decides identity.  The empty string, embedded NUL
+ * bytes and non-UTF-8 bytes are legal.  Ids are opaque; callers may assume
+ * only id >= 0 (never the engines' EMPTY_KEY).
+ *
+ * Hashes: hashes_out / d_hashes_out may be NULL; otherwise they receive a
+ * 64-bit content hash per row, a pure function of the bytes, identical
+ * across handles, devices and hash_bits.  Ids are per handle, so a keyed
+ * shuffle must partition on this hash, never on the ids.
+ *
+ * The device surface takes device pointers, runs on the handle's own stream
+ * and synchronises before returning, so a chained *_process_batch_device on
+ * another handle may consume d_ids_out directly.
+ *
+ * decode gathers on the device and returns malloc'd host buffers; an id that
+ * was never issued, or a total above INT32_MAX bytes, is an error.  A full
+ * dictionary ("capacity") or arena ("arena") is an error; strings interned
+ * by earlier calls stay valid, ids_out of the failing call are undefined.
+ *
+ * checkpoint_drain returns every interned string with its id; restore loads
+ * that into an EMPTY handle (anything else is an error) so every string
+ * keeps its id.  An id is a slot of the hash table, so the restoring handle
+ * needs the same log2_capacity and hash_bits; a mismatch is an error and
+ * leaves the handle empty.
+ *
+ * Out of scope: LargeUtf8 (int64 offsets); NULL keys (no validity bitmap is
+ * accepted, as with every other family); eviction (ids must stay stable for
+ * live state, as for the composite-key dictionary); the oracle has no
+ * counterpart -- a host dictionary is the checker for an interner. */
+void *arroyo_amd_strkey_create(const AmdStrKeyConfig *cfg);
+int arroyo_amd_strkey_encode(void *h, const int32_t *offsets,
+                             const uint8_t *data, int64_t n_rows,
+                             int64_t *ids_out, uint64_t *hashes_out);
+int arroyo_amd_strkey_encode_device(void *h, const int32_t *d_offsets,
+                                    const uint8_t *d_data, int64_t n_rows,
+                                    int64_t *d_ids_out,
+                                    uint64_t *d_hashes_out);
+int arroyo_amd_strkey_decode(void *h, const int64_t *ids, int64_t n_rows,
+                             AmdStrBatch *out);
+int arroyo_amd_strkey_count(void *h, int64_t *n_strings, int64_t *arena_used);
+int arroyo_amd_strkey_checkpoint_drain(void *h, AmdStrBatch *out);
+int arroyo_amd_strkey_restore(void *h, const int64_t *ids,
+                              const int32_t *offsets, const uint8_t *data,
+                              int64_t n_rows);
+/* Measurement aid: enable > 0 makes every later encode time its lookup
+ * (probe) kernel alone with HIP events, enable == 0 stops that, enable < 0
+ * leaves the setting; *last_lookup_ms (may be NULL) receives the kernel time
+ * of the last timed encode. */
+int arroyo_amd_strkey_profile(void *h, int enable, double *last_lookup_ms);
+void arroyo_amd_strkey_free_out(AmdStrBatch *out);
+void arroyo_amd_strkey_destroy(void *h);
+const char *arroyo_amd_strkey_last_error(void *h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -364,6 +364,34 @@ typedef struct {
     uint8_t **validity;
 } AmdOutBatch;
 
+/* Device string-key dictionary configuration (arroyo_amd_strkey_*).  The
+ * reference keys its state maps on arbitrary Arrow types by row-encoding the
+ * key tuple (crates/arroyo-state/src/tables/expiring_time_key_map.rs
+ * :1008-1049); here an Arrow Utf8 key column is interned on device to stable
+ * non-negative i64 ids that every operator above accepts as a key column.
+ * At most 7/8 of the 1 << log2_capacity slots are used (half or less keeps
+ * probes short); each interned string takes its length rounded up to 8 bytes
+ * of the arena. */
+typedef struct {
+    int32_t device;
+    int32_t log2_capacity;   /* hash slots = 1 << log2_capacity (1..30) */
+    int64_t arena_bytes;     /* device byte arena for interned strings */
+    int32_t hash_bits;       /* 0 = use the full 64-bit hash; k in 1..63 = keep
+                              * only the low k bits of the hash for slot
+                              * choice AND tag (forces collisions; exists so
+                              * exactness-under-collision is testable) */
+} AmdStrKeyConfig;
+
+/* Strings out (decode and checkpoint drain), allocated by the callee in
+ * host memory; free with arroyo_amd_strkey_free_out.  Arrow Utf8 layout. */
+typedef struct {
+    int64_t  n_rows;
+    int64_t *ids;            /* [n_rows] (drain: the id of each string;
+                              * decode: echo of the request) */
+    int32_t *offsets;        /* [n_rows + 1], offsets[0] == 0 */
+    uint8_t *data;           /* [offsets[n_rows]] */
+} AmdStrBatch;
+
 #ifdef __cplusplus
 }
 #endif
