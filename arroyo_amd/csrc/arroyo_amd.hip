@@ -797,8 +797,9 @@ template __global__ void k_update_packed<true, false>(UpdateArgs);
 template __global__ void k_update_packed<false, false>(UpdateArgs);
 
 /* ------------------------------------------------------------------ */
-/* Batched-probe update kernel (upd_kind 3, the default for the keyed
- * single-COUNT shape).  Measurement drove this shape: the wave-combine
+/* Batched-probe update kernel (upd_kind 3, ARROYO_AMD_UPD=batch; the
+ * default for the keyed single-COUNT shape before k_update_tile, which
+ * reuses its row path).  Measurement drove this shape: the wave-combine
  * variant's per-row ballots made every row cost the wave max(lane
  * latencies) — the wave could not start row i+1 until the slowest cold
  * lane's global probe for row i landed (107 us vs the LDS kernel's 71 us
@@ -1219,6 +1220,182 @@ k_update_batch_n(UpdateArgs A) {
 template __global__ void k_update_batch_n<8>(UpdateArgs);
 template __global__ void k_update_batch_n<12>(UpdateArgs);
 template __global__ void k_update_batch_n<16>(UpdateArgs);
+
+/* ------------------------------------------------------------------ */
+/* Tile update kernel (upd_kind 5, the default for the keyed single-COUNT
+ * shape).  A time-ordered stream is local: all occurrences of a nexmark
+ * cold key fall inside one ~1.5K-row stretch of the input, so a block that
+ * owns a CONTIGUOUS span of rows sees every occurrence of most of its keys.
+ * Block b owns row-vectors [b*S*256, (b+1)*S*256): S consecutive sub-tiles
+ * of 256 x Q rows, aggregated into one hashed linear-probing LDS table
+ * that lives for the whole span and is flushed once.  Rows that find no
+ * slot within PROBES take k_update_batch_n's MLP-batched global path.
+ * Counts model and measurements: profiles/tile_update_note.md. */
+
+/* Claim protocol as in lds_update_row: CAS the key, then publish the pane.
+ * A reader that sees the key with the pane still unset (or another pane)
+ * moves on to the next probe; it never adds into a slot whose pane it
+ * cannot see.  One (key, pane) may so end up in two slots — harmless, the
+ * flush adds both.  Returns true when the rows were absorbed. */
+template <int SLOTS, int PROBES>
+__device__ inline bool lds_tile_try(int64_t *ls_key, uint32_t *ls_pane,
+                                    uint32_t *ls_cnt, int64_t key,
+                                    uint32_t pane, uint32_t cnt) {
+    uint32_t h = (uint32_t)hash64((uint64_t)key * 2654435761u + pane);
+#pragma unroll
+    for (int pr = 0; pr < PROBES; pr++) {
+        uint32_t s = (h + pr) & (SLOTS - 1);
+        int64_t lk = ls_key[s];
+        if (lk == EMPTY_KEY) {
+            int64_t old = (int64_t)atomicCAS((unsigned long long *)&ls_key[s],
+                                             (unsigned long long)EMPTY_KEY,
+                                             (unsigned long long)key);
+            if (old == EMPTY_KEY) {
+                ls_pane[s] = pane;
+                atomicAdd(&ls_cnt[s], cnt);
+                return true;
+            }
+            lk = old;
+        }
+        if (lk == key && ls_pane[s] == pane) {
+            atomicAdd(&ls_cnt[s], cnt);
+            return true;
+        }
+    }
+    return false;
+}
+
+template <int Q, int SLOTS, int PROBES>
+__global__ void __launch_bounds__(256)
+k_update_tile(UpdateArgs A, int S) {
+    __shared__ int64_t ls_key[SLOTS];
+    __shared__ uint32_t ls_pane[SLOTS];
+    __shared__ uint32_t ls_cnt[SLOTS];
+    for (int i = threadIdx.x; i < SLOTS; i += 256) {
+        ls_key[i] = EMPTY_KEY;
+        ls_pane[i] = PANE_UNSET;
+        ls_cnt[i] = 0;
+    }
+    __syncthreads();
+    uint64_t local_min = ~0ULL, last_bin = EMPTY_TAG;
+    int64_t last_key = EMPTY_KEY;
+    uint32_t last_pane = PANE_UNSET;
+    uint64_t *last_cnt = nullptr;
+    const int64_t nq = A.n_rows / Q;
+    const uint64_t m = A.ring.C - 1;
+    int64_t v = (int64_t)blockIdx.x * S * 256 + threadIdx.x;
+    for (int t = 0; t < S && v < nq; t++, v += 256) {
+        int64_t key[Q];
+        uint64_t traw[Q];
+#pragma unroll
+        for (int j = 0; j < Q / 2; j++) {
+            ulonglong2 tp = ((const ulonglong2 *)A.ts_col)[(Q / 2) * v + j];
+            ulonglong2 kp = ((const ulonglong2 *)A.key_col)[(Q / 2) * v + j];
+            traw[2 * j] = tp.x;
+            traw[2 * j + 1] = tp.y;
+            key[2 * j] = (int64_t)kp.x;
+            key[2 * j + 1] = (int64_t)kp.y;
+        }
+        bool need[Q];
+        uint32_t pane[Q];
+        uint32_t cnt[Q];
+#pragma unroll
+        for (int j = 0; j < Q; j++) {
+            pane[j] = 0;
+            need[j] = row_prep(A, traw[j], key[j], local_min, last_bin,
+                               pane[j]);
+            cnt[j] = 1;
+        }
+#pragma unroll
+        for (int j = Q - 1; j >= 1; j--)
+            if (need[j] && need[j - 1] && key[j] == key[j - 1] &&
+                pane[j] == pane[j - 1]) {
+                cnt[j - 1] += cnt[j];
+                need[j] = false;
+            }
+#pragma unroll
+        for (int j = 0; j < Q; j++)
+            if (need[j] && key[j] == last_key && pane[j] == last_pane &&
+                last_cnt) {
+                atomicAdd((unsigned long long *)last_cnt,
+                          (unsigned long long)cnt[j]);
+                need[j] = false;
+            }
+#pragma unroll
+        for (int j = 0; j < Q; j++)
+            if (need[j] &&
+                lds_tile_try<SLOTS, PROBES>(ls_key, ls_pane, ls_cnt, key[j],
+                                            pane[j], cnt[j]))
+                need[j] = false;
+        uint64_t h[Q];
+        int64_t firstk[Q];
+#pragma unroll
+        for (int j = 0; j < Q; j++)
+            if (need[j]) {
+                h[j] = hash64((uint64_t)key[j]) & m;
+                firstk[j] = A.ring.keys[(size_t)pane[j] * A.ring.C + h[j]];
+            }
+#pragma unroll
+        for (int j = 0; j < Q; j++) {
+            if (!need[j]) continue;
+            uint64_t *c = probe_resolve(
+                A.ring.keys + (size_t)pane[j] * A.ring.C,
+                A.ring.state + (size_t)pane[j] * A.ring.C * 2, A.ring.C,
+                A.ring.err, key[j], h[j], firstk[j]);
+            if (c) {
+                atomicAdd((unsigned long long *)c,
+                          (unsigned long long)cnt[j]);
+                last_key = key[j];
+                last_pane = pane[j];
+                last_cnt = c;
+            }
+        }
+    }
+    fold_min_bin(local_min, A.ring.min_bin);
+    __syncthreads();
+    /* flush: each thread owns SLOTS/256 slots and issues the first-probe
+     * key loads of all its occupied slots before resolving any of them
+     * (the row loop's trick; the old flush was one dependent probe chain
+     * per slot) */
+    constexpr int NF = SLOTS / 256;
+    int64_t fkey[NF], ffirst[NF];
+    uint32_t fpane[NF];
+    uint64_t fh[NF];
+#pragma unroll
+    for (int j = 0; j < NF; j++) {
+        int s = threadIdx.x + j * 256;
+        fkey[j] = ls_key[s];
+        fpane[j] = ls_pane[s];
+        fh[j] = 0;
+        ffirst[j] = 0;
+        if (fkey[j] != EMPTY_KEY) {
+            fh[j] = hash64((uint64_t)fkey[j]) & m;
+            ffirst[j] = A.ring.keys[(size_t)fpane[j] * A.ring.C + fh[j]];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NF; j++) {
+        if (fkey[j] == EMPTY_KEY) continue;
+        uint64_t *c = probe_resolve(
+            A.ring.keys + (size_t)fpane[j] * A.ring.C,
+            A.ring.state + (size_t)fpane[j] * A.ring.C * 2, A.ring.C,
+            A.ring.err, fkey[j], fh[j], ffirst[j]);
+        if (c)
+            atomicAdd((unsigned long long *)c,
+                      (unsigned long long)ls_cnt[threadIdx.x + j * 256]);
+    }
+}
+
+/* 1024 slots x 4 probes won the {512,1024,2048} x {2,4} sweep at the bench
+ * shape (16 KB of LDS per block) */
+#define TILE_SLOTS 1024
+#define TILE_PROBES 4
+template __global__ void k_update_tile<8, TILE_SLOTS, TILE_PROBES>(UpdateArgs,
+                                                                   int);
+template __global__ void k_update_tile<12, TILE_SLOTS, TILE_PROBES>(UpdateArgs,
+                                                                    int);
+template __global__ void k_update_tile<16, TILE_SLOTS, TILE_PROBES>(UpdateArgs,
+                                                                    int);
 
 /* ------------------------------------------------------------------ */
 /* Radix-regroup update path (upd_kind 4).  The batched kernel is bound
@@ -2638,7 +2815,7 @@ struct GpuOp {
 
     int use_lds;
     int upd_kind;   /* 0 lds, 1 packed AoS, 2 split wave-combine,
-                       3 batched-probe, 4 radix-regroup */
+                       3 batched-probe, 4 radix-regroup, 5 tile */
     /* closed-pane index (see CpiBuildArgs) */
     uint64_t *cpi_entries;      /* [R][NR][cpi_range][cpi_ew] */
     uint32_t *cpi_cnt;          /* [R][NR] */
@@ -2669,6 +2846,8 @@ struct GpuOp {
     size_t rdx_tmp_bytes;
     int64_t rdx_cap;
     int force_blocks;
+    int tile_resident = 0;    /* k_update_tile blocks the device holds at once */
+    int tile_resident_q = 0;  /* ... queried for this rows-per-thread */
     int kmode;
     int use_vec;
     int use_wavecmb = 0;
@@ -2917,17 +3096,19 @@ API void *arroyo_amd_create(const AmdWindowConfig *cfg) {
      * headline): "split" = wave-combine no-LDS kernel over the standard
      * split key/state arrays (default; key probes stay L2-clean),
      * "packed" = the same kernel over an AoS {key,count} table,
-     * "lds" = the round-1 LDS-staged kernel.  See k_update_packed. */
+     * "lds" = the round-1 LDS-staged kernel (see k_update_packed),
+     * "batch" = k_update_batch_n, "tile" = k_update_tile (default). */
     bool count_shape = (o->cfg.n_keys == 1 && o->agg.n_aggs == 1 &&
                         o->agg.op[0] == AMD_AGG_COUNT && !o->use_radix &&
                         o->kmode == 0);
-    o->upd_kind = count_shape ? 3 : 0;
+    o->upd_kind = count_shape ? 5 : 0;
     if (const char *ev = getenv("ARROYO_AMD_UPD")) {
         if (!strcmp(ev, "lds")) o->upd_kind = 0;
         else if (count_shape && !strcmp(ev, "packed")) o->upd_kind = 1;
         else if (count_shape && !strcmp(ev, "split")) o->upd_kind = 2;
         else if (count_shape && !strcmp(ev, "batch")) o->upd_kind = 3;
         else if (count_shape && !strcmp(ev, "rdx2")) o->upd_kind = 4;
+        else if (count_shape && !strcmp(ev, "tile")) o->upd_kind = 5;
     }
     if (const char *ev = getenv("ARROYO_AMD_PACKED"))   /* legacy alias */
         if (!atoi(ev)) o->upd_kind = 0;
@@ -3287,18 +3468,60 @@ static int launch_update(GpuOp *o, const int64_t *const *dcols, int64_t n_rows,
     if (o->upd_kind != 0) {
         bool pvec = n_rows >= 2 && ((uintptr_t)A.ts_col & 15) == 0 &&
                     ((uintptr_t)A.key_col & 15) == 0;
-        int64_t punits = pvec ? (n_rows + 1) / (o->upd_kind == 3 ? 4 : 2)
-                              : n_rows;
+        bool batched = o->upd_kind == 3 || o->upd_kind == 5;
+        int64_t punits = pvec ? (n_rows + 1) / (batched ? 4 : 2) : n_rows;
         int64_t pwant = (punits + 255) / 256;
         int pcap = 2048;
         if (const char *ev2 = getenv("ARROYO_AMD_PBLOCKS")) pcap = atoi(ev2);
         int pblocks = (int)(pwant > pcap ? pcap : (pwant < 1 ? 1 : pwant));
         if (o->force_blocks > 0) pblocks = o->force_blocks;
-        if (o->upd_kind == 3) {
+        if (batched) {
             int bq = 8;
             if (const char *ev3 = getenv("ARROYO_AMD_BQ")) bq = atoi(ev3);
             if (!pvec) bq = 1;
-            if (bq >= 16)
+            /* the row count each kernel thread takes per iteration */
+            bq = bq >= 16 ? 16 : bq >= 12 ? 12 : bq >= 8 ? 8
+               : bq >= 4 ? 4 : bq >= 2 ? 2 : 1;
+            if (o->upd_kind == 5 && bq >= 8) {
+                /* contiguous spans: block b owns sub-tiles [b*S, (b+1)*S) of
+                 * 256*bq rows.  The block budget only sets the span length,
+                 * so locality never depends on a grid cap.  By default the
+                 * budget is the number of blocks the device holds at once:
+                 * a launch that fits keeps one sub-tile per block, a larger
+                 * one grows the span until the grid is a single resident
+                 * wave (measured best at the bench's 3.5M-row launches:
+                 * S=2, profiles/tile_update_note.md).  PBLOCKS or a forced
+                 * block count replace the budget, TILE_S the span itself. */
+                auto kern = k_update_tile<8, TILE_SLOTS, TILE_PROBES>;
+                if (bq == 16)
+                    kern = k_update_tile<16, TILE_SLOTS, TILE_PROBES>;
+                else if (bq == 12)
+                    kern = k_update_tile<12, TILE_SLOTS, TILE_PROBES>;
+                if (o->tile_resident_q != bq) {
+                    int per_cu = 0, cus = 0;
+                    hipError_t e1 = hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                        &per_cu, kern, 256, 0);
+                    hipError_t e2 = hipDeviceGetAttribute(
+                        &cus, hipDeviceAttributeMultiprocessorCount,
+                        o->cfg.device);
+                    HIP_CHECK(o, e1);
+                    HIP_CHECK(o, e2);
+                    o->tile_resident = per_cu * cus > 0 ? per_cu * cus : 1;
+                    o->tile_resident_q = bq;
+                }
+                int64_t tiles = (n_rows / bq + 255) / 256;
+                if (tiles < 1) tiles = 1;
+                int64_t budget = o->tile_resident;
+                if (getenv("ARROYO_AMD_PBLOCKS")) budget = pcap;
+                if (o->force_blocks > 0) budget = o->force_blocks;
+                if (budget < 1) budget = 1;
+                int64_t span = (tiles + budget - 1) / budget;
+                if (const char *ev4 = getenv("ARROYO_AMD_TILE_S"))
+                    if (atoi(ev4) > 0) span = atoi(ev4);
+                int tblocks = (int)((tiles + span - 1) / span);
+                hipLaunchKernelGGL(kern, dim3(tblocks), dim3(256), 0,
+                                   o->stream, A, (int)span);
+            } else if (bq >= 16)
                 hipLaunchKernelGGL(k_update_batch_n<16>, dim3(pblocks),
                                    dim3(256), 0, o->stream, A);
             else if (bq >= 12)

@@ -274,7 +274,50 @@ def bench_ordered(which=("A", "B"), reps=10, warmup=2):
         print(json.dumps(res))
 
 
+def bench_window_update(which=("tile", "batch"), streams=("uniform", "nexmark"),
+                        n=54 * 65536, launches=24, windows=5):
+    """The window operator's COUNT update kernel alone, one 3.5M-row
+    device-resident launch at a time (the bench's fused launch size), per
+    ARROYO_AMD_UPD flavour.  "uniform" draws keys uniformly over 2^20 -- no
+    time locality, so a per-block table finds nothing to combine; "nexmark"
+    is the bench stream.  The same rows are replayed, so after the warm-up
+    every key is resident in its pane table.  Prints us per launch for each
+    of `windows` timed windows (host clock around `launches` launches that
+    end in a stream synchronise)."""
+    import torch
+    from arroyo_amd import cabi, gpu, nexmark
+    dev = torch.device("cuda", 0)
+    lib = gpu.lib()
+    nkey, ts = nexmark.bids(n, seed=42)
+    ukey = np.random.default_rng(5).integers(0, 1 << 20, size=n).astype(np.int64)
+    d_ts = torch.from_numpy(ts).to(dev)
+    for stream in streams:
+        d_key = torch.from_numpy(ukey if stream == "uniform" else nkey).to(dev)
+        for upd in which:
+            os.environ["ARROYO_AMD_UPD"] = upd
+            op = gpu.make_op(cabi.make_config(
+                width_ns=10 * NS, slide_ns=2 * NS, n_keys=1, n_value_cols=0,
+                aggs=[(cabi.COUNT, -1)], log2_capacity=22, ring_panes=16,
+                emit_to_host=False))
+            ptrs = [d_key.data_ptr(), d_ts.data_ptr()]
+            us = []
+            for w in range(windows + 1):          # window 0 warms up
+                lib.arroyo_amd_sync(op._h)
+                t0 = time.perf_counter()
+                for _ in range(launches):
+                    op.process_batch_device(ptrs, n)
+                lib.arroyo_amd_sync(op._h)
+                if w:
+                    us.append((time.perf_counter() - t0) * 1e6 / launches)
+            op.close()
+            print(f"window_update {stream} {upd}: us per {n}-row launch "
+                  f"{' '.join(f'{u:.1f}' for u in us)} "
+                  f"(median {float(np.median(us)):.1f})")
+    os.environ.pop("ARROYO_AMD_UPD", None)
+
+
 LEGS = {"expjoin": bench_expjoin, "updagg": bench_updagg,
+        "window_update": bench_window_update,
         "expjoin_device": bench_expjoin_device,
         "updagg_device": bench_updagg_device,
         "updagg_nullable_device": bench_updagg_nullable_device,
