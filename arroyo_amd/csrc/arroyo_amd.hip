@@ -16,7 +16,7 @@
  * MI355X-first design (NOT a translation of the reference's
  * sort+take+DataFusion-stream structure):
  *   - Window state is a device-resident ring of per-pane open-addressing
- *     hash tables in HBM.  One fused kernel (k_update) replaces K1+K2+K3:
+ *     hash tables in HBM.  One fused update kernel replaces K1+K2+K3:
  *     per row it computes the bin (ts - ts % slide), applies the late-data
  *     drop, claims the pane's ring slot, and atomically updates the
  *     (key -> partial state) entry.  The reference's comparison sort +
@@ -42,7 +42,6 @@
  * pinned against the reference's golden vectors) by tests/test_gpu_parity.py.
  */
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <cstdio>
 #include <cstdlib>
@@ -69,12 +68,8 @@
 enum WordOp { W_ADD_I64 = 0, W_MAX_U64 = 1, W_ADD_F64 = 2, W_NONE = 3 };
 
 struct DeviceRing {
-    int64_t  *keys;      /* [R][C] (unpacked layout; null when packed) */
-    uint64_t *state;     /* [R][C][n_aggs][2] encoded (null when packed) */
-    uint64_t *slots;     /* [R][C][2] = {key, count} AoS (packed layout:
-                            single-COUNT keyed shape; one 64B line holds
-                            both probe key and its state word, halving the
-                            random-access line touches of the hot kernel) */
+    int64_t  *keys;      /* [R][C] */
+    uint64_t *state;     /* [R][C][n_aggs][2] encoded */
     uint64_t *tag;       /* [R] bin nanos or EMPTY_TAG */
     /* special entry per pane for an actual key == EMPTY_KEY */
     uint32_t *spec_used; /* [R] */
@@ -83,7 +78,6 @@ struct DeviceRing {
     uint64_t *min_bin;   /* running min of non-late bins (state machine) */
     uint32_t  C;         /* slots per pane, power of two */
     uint32_t  R;         /* panes in ring, power of two */
-    int       packed;    /* 1: use `slots`, keys/state are null */
 };
 
 struct AggSpec {
@@ -310,8 +304,6 @@ struct UpdateArgs {
     uint64_t ts_offset;  /* added to ts (bench ring replay); 0 otherwise */
     DeviceRing ring;
     AggSpec agg;
-    int mode;  /* debug stage isolation: 0 full, 1 read+bin only,
-                  2 +tag protocol, 3 +table upsert (no state update) */
 };
 
 __device__ inline void fold_min_bin(uint64_t local_min, uint64_t *min_bin) {
@@ -330,43 +322,6 @@ __device__ inline void fold_min_bin(uint64_t local_min, uint64_t *min_bin) {
             atomicMin((unsigned long long *)min_bin,
                       (unsigned long long)local_min);
     }
-}
-
-__global__ void __launch_bounds__(256)
-k_update(UpdateArgs A) {
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const int64_t *const *vc = A.vcols;
-    uint64_t local_min = ~0ULL, last_bin = EMPTY_TAG;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-         i < A.n_rows; i += stride) {
-        uint64_t t = (uint64_t)A.ts_col[i] + A.ts_offset;
-        uint64_t q = div_slide(t, A.slide, A.slide_inv);
-        uint64_t bin = q * A.slide;
-        if (A.has_wm && bin < A.wm_bin) continue;           /* late drop */
-        if (bin < local_min) local_min = bin;
-        if (A.mode == 1) continue;
-        uint32_t p = (uint32_t)(q & (A.ring.R - 1));
-        if (bin != last_bin) {
-            claim_tag_wave(A.ring.tag, p, bin, EMPTY_TAG, A.ring.err);
-            last_bin = bin;
-        }
-        if (A.mode == 2) continue;
-        int64_t key = A.key_col ? A.key_col[i] : 0;
-        uint64_t *st;
-        if (key == EMPTY_KEY) {
-            atomicExch(&A.ring.spec_used[p], 1u);
-            st = A.ring.spec_state + (size_t)p * A.agg.n_aggs * 2;
-        } else {
-            int64_t *keys = A.ring.keys + (size_t)p * A.ring.C;
-            int64_t s = table_upsert(keys, A.ring.C, key, A.ring.err);
-            if (s < 0) continue;
-            st = A.ring.state +
-                 ((size_t)p * A.ring.C + (size_t)s) * A.agg.n_aggs * 2;
-        }
-        if (A.mode == 3) continue;
-        atomic_update(st, A.agg, vc, i);
-    }
-    fold_min_bin(local_min, A.ring.min_bin);
 }
 
 /* pure streaming-read calibration kernel: 16 B/lane vector loads of both
@@ -398,35 +353,16 @@ k_stream_sum(const ulonglong2 *a, const ulonglong2 *b, int64_t n2,
  * table (cutting global atomic traffic on hot keys -- nexmark sends ~50% of
  * bids to one auction), then flushes distinct (pane,key) entries to the
  * ring.  Entries evicted on LDS collision fall through to global atomics. */
-#define LDS_SLOTS 1024   /* default; x (8B key + 4B pane + n_aggs*16B) */
+#define LDS_SLOTS 1024   /* x (8B key + 4B pane + n_aggs*16B) */
 
 #define PANE_UNSET 0xFFFFFFFFu
-
-/* wavefront same-slot combining (ARROYO_AMD_WAVECMB=1, COUNT-only path):
- * group the wave's lanes by resolved LDS slot and issue ONE atomicAdd of
- * the group's popcount per distinct slot, instead of up to 64 serialized
- * same-address LDS atomics when a hot key dominates the wave.  The loop
- * runs (distinct slots in wave) iterations of ballot+shfl. */
-__device__ inline void wave_count_combine(int slot, uint64_t *ls_st) {
-    unsigned long long act = __ballot(slot >= 0);
-    const unsigned lane = threadIdx.x & 63u;
-    while (act) {
-        int lead = __ffsll((unsigned long long)act) - 1;
-        int ls = __shfl(slot, lead, 64);
-        unsigned long long grp = __ballot(slot == ls) & act;
-        if (slot == ls && lane == (unsigned)lead)
-            atomicAdd((unsigned long long *)(ls_st + (size_t)ls * 2),
-                      (unsigned long long)__popcll(grp));
-        act &= ~grp;
-    }
-}
 
 /* per-row body shared by the scalar and vectorized LDS kernels.
  * COUNT_ONLY specializes the hot q5 shape (single COUNT(*)) away from the
  * aggregate-spec loop; last_key/last_slot cache skips hash+probe when
  * consecutive rows repeat a key (the nexmark hot auction makes runs
  * common). */
-template <int SLOTS, bool COUNT_ONLY, bool WAVECMB = false>
+template <int SLOTS, bool COUNT_ONLY>
 __device__ inline void lds_update_row(const UpdateArgs &A, int64_t *ls_key,
                                       uint32_t *ls_pane, uint64_t *ls_st,
                                       int64_t row, uint64_t traw, int64_t key,
@@ -440,7 +376,6 @@ __device__ inline void lds_update_row(const UpdateArgs &A, int64_t *ls_key,
     uint64_t bin = q * A.slide;
     if (A.has_wm && bin < A.wm_bin) return;
     if (bin < local_min) local_min = bin;
-    if (A.mode == 1) return;
     uint32_t p = (uint32_t)(q & (A.ring.R - 1));
     /* register-cached bin: the tag claim (and its global tag read) runs
      * once per thread per bin transition, not once per row */
@@ -448,26 +383,18 @@ __device__ inline void lds_update_row(const UpdateArgs &A, int64_t *ls_key,
         claim_tag_wave(A.ring.tag, p, bin, EMPTY_TAG, A.ring.err);
         last_bin = bin;
     }
-    if (A.mode == 2) return;
-    const int na2 = COUNT_ONLY ? 1 : na;
-    (void)na2;
-    int cslot = -1;  /* WAVECMB: resolved LDS slot, combined below */
     /* same (key, pane) as the previous row: reuse the cached LDS slot */
     if (key == last_key && last_slot != PANE_UNSET &&
         ls_pane[last_slot] == p) {
         if (COUNT_ONLY) {
-            if (WAVECMB) {
-                cslot = (int)last_slot;
-            } else {
-                atomicAdd((unsigned long long *)
-                              (ls_st + (size_t)last_slot * 2), 1ULL);
-                return;
-            }
+            atomicAdd((unsigned long long *)
+                          (ls_st + (size_t)last_slot * 2), 1ULL);
+            return;
         }
     }
     /* try the LDS table first, fall through to global */
     bool done = false;
-    if (!(WAVECMB && cslot >= 0) && key != EMPTY_KEY) {
+    if (key != EMPTY_KEY) {
         uint32_t h = (uint32_t)hash64((uint64_t)key * 0x9e37u + p) &
                      (SLOTS - 1);
         for (int pr = 0; pr < 4 && !done; pr++) {
@@ -491,11 +418,7 @@ __device__ inline void lds_update_row(const UpdateArgs &A, int64_t *ls_key,
             if (k == key && (claimed || ls_pane[s] == p)) {
                 uint64_t *st = ls_st + (size_t)s * na * 2;
                 if (COUNT_ONLY) {
-                    if (WAVECMB) {
-                        cslot = (int)s;
-                    } else {
-                        atomicAdd((unsigned long long *)st, 1ULL);
-                    }
+                    atomicAdd((unsigned long long *)st, 1ULL);
                     last_key = key;
                     last_slot = s;
                     done = true;
@@ -505,10 +428,6 @@ __device__ inline void lds_update_row(const UpdateArgs &A, int64_t *ls_key,
                 done = true;
             }
         }
-    }
-    if (WAVECMB && COUNT_ONLY) {
-        wave_count_combine(cslot, ls_st);
-        if (cslot >= 0) return;
     }
     if (!done) {
         uint64_t *st;
@@ -580,7 +499,7 @@ k_update_lds(UpdateArgs A) {
  * per thread per iteration -- requires 16 B-aligned column pointers (host
  * checks).  Fewer, fatter waves: wave-dispatch cost was measurable at one
  * 8 B load per thread. */
-template <int SLOTS, bool COUNT_ONLY, bool WAVECMB = false>
+template <int SLOTS, bool COUNT_ONLY>
 __global__ void __launch_bounds__(256)
 k_update_lds_vec(UpdateArgs A) {
     __shared__ int64_t  ls_key[SLOTS];
@@ -601,15 +520,15 @@ k_update_lds_vec(UpdateArgs A) {
             k0 = (int64_t)kv.x;
             k1 = (int64_t)kv.y;
         }
-        lds_update_row<SLOTS, COUNT_ONLY, WAVECMB>(
+        lds_update_row<SLOTS, COUNT_ONLY>(
             A, ls_key, ls_pane, ls_st, 2 * v, tsv.x, k0, local_min,
             last_bin, last_key, last_slot);
-        lds_update_row<SLOTS, COUNT_ONLY, WAVECMB>(
+        lds_update_row<SLOTS, COUNT_ONLY>(
             A, ls_key, ls_pane, ls_st, 2 * v + 1, tsv.y, k1, local_min,
             last_bin, last_key, last_slot);
     }
     if ((A.n_rows & 1) && blockIdx.x == 0 && threadIdx.x == 0)
-        lds_update_row<SLOTS, COUNT_ONLY, WAVECMB>(A, ls_key, ls_pane,
+        lds_update_row<SLOTS, COUNT_ONLY>(A, ls_key, ls_pane,
                                           ls_st, A.n_rows - 1,
                                           (uint64_t)A.ts_col[A.n_rows - 1],
                                           A.key_col ? A.key_col[A.n_rows - 1]
@@ -621,194 +540,22 @@ k_update_lds_vec(UpdateArgs A) {
     lds_flush<SLOTS>(A, ls_key, ls_pane, ls_st);
 }
 
-template __global__ void k_update_lds_vec<1024, false>(UpdateArgs);
-template __global__ void k_update_lds_vec<2048, false>(UpdateArgs);
-template __global__ void k_update_lds_vec<1024, true>(UpdateArgs);
-template __global__ void k_update_lds_vec<2048, true>(UpdateArgs);
-template __global__ void k_update_lds_vec<1024, true, true>(UpdateArgs);
-template __global__ void k_update_lds_vec<2048, true, true>(UpdateArgs);
+template __global__ void k_update_lds_vec<LDS_SLOTS, false>(UpdateArgs);
+template __global__ void k_update_lds_vec<LDS_SLOTS, true>(UpdateArgs);
 
 /* ------------------------------------------------------------------ */
-/* Packed-table update path (default for the keyed single-COUNT shape —
- * the q5 headline).  Round-2 redesign from measurement: the LDS-staged
- * kernel was latency-bound, not bandwidth-bound (PMC traffic ~2.9x
- * compulsory but only ~7% of peak) — the cost was ~1M+ random global
- * upserts per launch (per-block LDS flush x 640 blocks + cold-key
- * fallthrough), each touching TWO cache lines (key array + state array)
- * with a returning atomic.  This path instead:
- *   - stores the pane table AoS ({key, count} in one 16B slot): the probe
- *     load brings the count word in the same 64B line, and the count
- *     atomicAdd's result is unused so it compiles to a no-return
- *     global_atomic_add (fire-and-forget; no latency chain);
- *   - uses NO LDS staging and therefore has NO per-block flush: the
- *     nexmark hot key is wave-uniform (consecutive rows -> one wave), so
- *     two ballot samples (first/last pending lane) find the hot group and
- *     its leader issues ONE atomicAdd(popcount) for the whole group;
- *     cold keys (~unique; zero reuse, which is why LDS staging bought
- *     nothing for them) go straight to the packed table;
- *   - keeps a per-thread (key,pane)->slot register cache for
- *     intra-thread runs (the vectorized 2-rows-per-iteration pairs). */
-
-__device__ inline uint64_t *packed_upsert(uint64_t *slots, uint32_t C,
-                                          int64_t key, int *err) {
-    uint64_t m = C - 1;
-    uint64_t i = hash64((uint64_t)key) & m;
-    uint32_t lim = C < MAX_PROBES ? C : MAX_PROBES;
-    for (uint32_t probes = 0; probes < lim; probes++) {
-        uint64_t *s = slots + i * 2;
-        int64_t k = (int64_t)s[0];
-        if (k == key) return s + 1;
-        if (k == EMPTY_KEY) {
-            int64_t old = (int64_t)atomicCAS((unsigned long long *)s,
-                                             (unsigned long long)EMPTY_KEY,
-                                             (unsigned long long)key);
-            if (old == EMPTY_KEY || old == key) return s + 1;
-        }
-        i = (i + 1) & m;
-    }
-    *err = ERR_TABLE_FULL;
-    return nullptr;
-}
-
-#define HOT_MIN 4   /* combine a wave group only when >= this many lanes */
-
-/* find-or-claim the count word for (pane p, key).  PACKED: one {key,count}
- * line (fewest line touches, but count atomics keep the probe lines dirty).
- * split (!PACKED): probe the read-only key array (stays clean and
- * L2-cacheable under concurrent updates) and add to the separate state
- * array. */
-template <bool PACKED>
-__device__ inline uint64_t *count_upsert(const DeviceRing &ring, uint32_t p,
-                                         int64_t key) {
-    if (PACKED)
-        return packed_upsert(ring.slots + (size_t)p * ring.C * 2, ring.C,
-                             key, ring.err);
-    int64_t s = table_upsert(ring.keys + (size_t)p * ring.C, ring.C, key,
-                             ring.err);
-    if (s < 0) return nullptr;
-    return ring.state + ((size_t)p * ring.C + (size_t)s) * 2;
-}
-
-/* one row of the packed path; called by every active lane together (the
- * ballots inside require it), rows that drop out carry need=false */
-template <bool PACKED>
-__device__ inline void packed_row(const UpdateArgs &A, uint64_t traw,
-                                  int64_t key, uint64_t &local_min,
-                                  uint64_t &last_bin, int64_t &last_key,
-                                  uint32_t &last_pane, uint64_t *&last_cnt) {
-    uint64_t t = traw + A.ts_offset;
-    uint64_t q = div_slide(t, A.slide, A.slide_inv);
-    uint64_t bin = q * A.slide;
-    bool alive = !(A.has_wm && bin < A.wm_bin);      /* late drop */
-    if (alive && bin < local_min) local_min = bin;
-    uint32_t p = (uint32_t)(q & (A.ring.R - 1));
-    if (alive && bin != last_bin) {
-        claim_tag_wave(A.ring.tag, p, bin, EMPTY_TAG, A.ring.err);
-        last_bin = bin;
-    }
-    bool need = alive;
-    if (need && key == EMPTY_KEY) {                  /* sentinel-valued key */
-        atomicExch(&A.ring.spec_used[p], 1u);
-        atomicAdd((unsigned long long *)
-                      (A.ring.spec_state + (size_t)p * 2), 1ULL);
-        need = false;
-    }
-    /* intra-thread run cache (vec pairs, bursty keys) */
-    if (need && key == last_key && p == last_pane && last_cnt) {
-        atomicAdd((unsigned long long *)last_cnt, 1ULL);
-        need = false;
-    }
-    /* wave-hot combine: sample the first and last pending lanes; if >=
-     * HOT_MIN lanes share that (key, bin), the group leader does one
-     * upsert + one atomicAdd(count_of_group) */
-    unsigned long long pend = __ballot(need);
-    const int lane = (int)(threadIdx.x & 63);
-    for (int s = 0; s < 2 && pend; s++) {
-        int sl = s == 0 ? (int)(__ffsll((long long)pend) - 1)
-                        : 63 - (int)__clzll((long long)pend);
-        int64_t k0 = (int64_t)__shfl((long long)key, sl, 64);
-        uint64_t b0 = (uint64_t)__shfl((long long)bin, sl, 64);
-        uint32_t pp = (uint32_t)__shfl((int)p, sl, 64);
-        bool mine = need && key == k0 && bin == b0;
-        unsigned long long grp = __ballot(mine);
-        int cnt = __popcll((long long)grp);
-        if (cnt >= HOT_MIN) {
-            if (mine && lane == (int)(__ffsll((long long)grp) - 1)) {
-                uint64_t *c = count_upsert<PACKED>(A.ring, pp, k0);
-                if (c) {
-                    atomicAdd((unsigned long long *)c,
-                              (unsigned long long)cnt);
-                    last_key = k0;
-                    last_pane = pp;
-                    last_cnt = c;
-                }
-            }
-            if (mine) need = false;
-            pend &= ~grp;
-        }
-    }
-    if (need) {
-        uint64_t *c = count_upsert<PACKED>(A.ring, p, key);
-        if (c) {
-            atomicAdd((unsigned long long *)c, 1ULL);
-            last_key = key;
-            last_pane = p;
-            last_cnt = c;
-        }
-    }
-}
-
-template <bool VEC, bool PACKED = true>
-__global__ void __launch_bounds__(256)
-k_update_packed(UpdateArgs A) {
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    uint64_t local_min = ~0ULL, last_bin = EMPTY_TAG;
-    int64_t last_key = EMPTY_KEY;
-    uint32_t last_pane = PANE_UNSET;
-    uint64_t *last_cnt = nullptr;
-    if (VEC) {
-        int64_t n2 = A.n_rows >> 1;
-        for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-             v < n2; v += stride) {
-            ulonglong2 tsv = ((const ulonglong2 *)A.ts_col)[v];
-            ulonglong2 kv = ((const ulonglong2 *)A.key_col)[v];
-            packed_row<PACKED>(A, tsv.x, (int64_t)kv.x, local_min, last_bin,
-                               last_key, last_pane, last_cnt);
-            packed_row<PACKED>(A, tsv.y, (int64_t)kv.y, local_min, last_bin,
-                               last_key, last_pane, last_cnt);
-        }
-        if ((A.n_rows & 1) && blockIdx.x == 0 && threadIdx.x == 0)
-            packed_row<PACKED>(A, (uint64_t)A.ts_col[A.n_rows - 1],
-                               A.key_col[A.n_rows - 1], local_min, last_bin,
-                               last_key, last_pane, last_cnt);
-    } else {
-        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-             i < A.n_rows; i += stride)
-            packed_row<PACKED>(A, (uint64_t)A.ts_col[i], A.key_col[i],
-                               local_min, last_bin, last_key, last_pane,
-                               last_cnt);
-    }
-    fold_min_bin(local_min, A.ring.min_bin);
-}
-
-template __global__ void k_update_packed<true, true>(UpdateArgs);
-template __global__ void k_update_packed<false, true>(UpdateArgs);
-template __global__ void k_update_packed<true, false>(UpdateArgs);
-template __global__ void k_update_packed<false, false>(UpdateArgs);
-
-/* ------------------------------------------------------------------ */
-/* Batched-probe update kernel (upd_kind 3, ARROYO_AMD_UPD=batch; the
+/* Batched-probe update kernel (UPD_BATCH, ARROYO_AMD_UPD=batch; the
  * default for the keyed single-COUNT shape before k_update_tile, which
- * reuses its row path).  Measurement drove this shape: the wave-combine
+ * reuses its row path).  Measurement drove this shape: a wave-combine
  * variant's per-row ballots made every row cost the wave max(lane
  * latencies) — the wave could not start row i+1 until the slowest cold
  * lane's global probe for row i landed (107 us vs the LDS kernel's 71 us
  * per 1.85M rows).  Here there is NO cross-lane coordination in the row
- * loop at all: each thread takes 4 consecutive rows per iteration,
+ * loop at all: each thread takes Q consecutive rows per iteration,
  * collapses sequential same-key runs (the nexmark hot key arrives in
  * runs), checks its register cache, then issues the remaining rows'
  * first probe loads back-to-back (independent -> memory-level
- * parallelism 4) before resolving any of them.  Count updates are
+ * parallelism Q) before resolving any of them.  Count updates are
  * no-return atomicAdds (fire-and-forget): same-address hot-key traffic
  * queues at the memory-side cache without stalling the wave (~9 adds/us
  * needed vs the measured ~88/us single-address ceiling). */
@@ -935,186 +682,12 @@ __device__ inline bool lds_hot_try(int64_t *ls_key, uint32_t *ls_pane,
     return false;
 }
 
-template <int Q>
-__global__ void __launch_bounds__(256)
-k_update_batch(UpdateArgs A) {
-    __shared__ int64_t ls_key[BATCH_LSLOTS];
-    __shared__ uint32_t ls_pane[BATCH_LSLOTS];
-    __shared__ unsigned long long ls_cnt[BATCH_LSLOTS];
-    for (int i = threadIdx.x; i < BATCH_LSLOTS; i += blockDim.x) {
-        ls_key[i] = EMPTY_KEY;
-        ls_pane[i] = PANE_UNSET;
-        ls_cnt[i] = 0;
-    }
-    __syncthreads();
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    uint64_t local_min = ~0ULL, last_bin = EMPTY_TAG;
-    int64_t last_key = EMPTY_KEY;
-    uint32_t last_pane = PANE_UNSET;
-    uint64_t *last_cnt = nullptr;
-    int64_t nq = A.n_rows / Q;
-    const uint64_t m = A.ring.C - 1;
-    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nq;
-         v += stride) {
-        /* row pair 0/1 (and 2/3 when Q == 4), written longhand: arrays +
-         * unrolled loops here ICEd clang-22's simplifycfg */
-        ulonglong2 tp0 = ((const ulonglong2 *)A.ts_col)[(Q / 2) * v];
-        ulonglong2 kp0 = ((const ulonglong2 *)A.key_col)[(Q / 2) * v];
-        ulonglong2 tp1 = tp0, kp1 = kp0;
-        if (Q == 4) {
-            tp1 = ((const ulonglong2 *)A.ts_col)[(Q / 2) * v + 1];
-            kp1 = ((const ulonglong2 *)A.key_col)[(Q / 2) * v + 1];
-        }
-        int64_t k0 = (int64_t)kp0.x, k1 = (int64_t)kp0.y;
-        int64_t k2 = (int64_t)kp1.x, k3 = (int64_t)kp1.y;
-        uint32_t p0 = 0, p1 = 0, p2 = 0, p3 = 0;
-        bool n0 = row_prep(A, tp0.x, k0, local_min, last_bin, p0);
-        bool n1 = row_prep(A, tp0.y, k1, local_min, last_bin, p1);
-        bool n2 = false, n3 = false;
-        if (Q == 4) {
-            n2 = row_prep(A, tp1.x, k2, local_min, last_bin, p2);
-            n3 = row_prep(A, tp1.y, k3, local_min, last_bin, p3);
-        }
-        /* collapse sequential same-key runs (the hot key arrives in runs) */
-        uint32_t c0 = 1, c1 = 1, c2 = 1, c3 = 1;
-        if (Q == 4 && n3 && n2 && k3 == k2 && p3 == p2) {
-            c2 += c3;
-            n3 = false;
-        }
-        if (Q == 4 && n2 && n1 && k2 == k1 && p2 == p1) {
-            c1 += c2;
-            n2 = false;
-        }
-        if (n1 && n0 && k1 == k0 && p1 == p0) {
-            c0 += c1;
-            n1 = false;
-        }
-        /* register cache from the previous quad */
-        if (n0 && k0 == last_key && p0 == last_pane && last_cnt) {
-            atomicAdd((unsigned long long *)last_cnt,
-                      (unsigned long long)c0);
-            n0 = false;
-        }
-        if (n1 && k1 == last_key && p1 == last_pane && last_cnt) {
-            atomicAdd((unsigned long long *)last_cnt,
-                      (unsigned long long)c1);
-            n1 = false;
-        }
-        if (Q == 4 && n2 && k2 == last_key && p2 == last_pane && last_cnt) {
-            atomicAdd((unsigned long long *)last_cnt,
-                      (unsigned long long)c2);
-            n2 = false;
-        }
-        if (Q == 4 && n3 && k3 == last_key && p3 == last_pane && last_cnt) {
-            atomicAdd((unsigned long long *)last_cnt,
-                      (unsigned long long)c3);
-            n3 = false;
-        }
-        /* per-block hot cache (LDS) */
-        if (n0 && lds_hot_try(ls_key, ls_pane, ls_cnt, k0, p0, c0))
-            n0 = false;
-        if (n1 && lds_hot_try(ls_key, ls_pane, ls_cnt, k1, p1, c1))
-            n1 = false;
-        if (Q == 4 && n2 && lds_hot_try(ls_key, ls_pane, ls_cnt, k2, p2, c2))
-            n2 = false;
-        if (Q == 4 && n3 && lds_hot_try(ls_key, ls_pane, ls_cnt, k3, p3, c3))
-            n3 = false;
-        /* issue every remaining row's first probe load before resolving
-         * any of them (memory-level parallelism across the quad) */
-        uint64_t h0 = 0, h1 = 0, h2 = 0, h3 = 0;
-        int64_t f0 = 0, f1 = 0, f2 = 0, f3 = 0;
-        if (n0) {
-            h0 = hash64((uint64_t)k0) & m;
-            f0 = A.ring.keys[(size_t)p0 * A.ring.C + h0];
-        }
-        if (n1) {
-            h1 = hash64((uint64_t)k1) & m;
-            f1 = A.ring.keys[(size_t)p1 * A.ring.C + h1];
-        }
-        if (Q == 4 && n2) {
-            h2 = hash64((uint64_t)k2) & m;
-            f2 = A.ring.keys[(size_t)p2 * A.ring.C + h2];
-        }
-        if (Q == 4 && n3) {
-            h3 = hash64((uint64_t)k3) & m;
-            f3 = A.ring.keys[(size_t)p3 * A.ring.C + h3];
-        }
-        if (n0) {
-            uint64_t *c = probe_resolve(
-                A.ring.keys + (size_t)p0 * A.ring.C,
-                A.ring.state + (size_t)p0 * A.ring.C * 2, A.ring.C,
-                A.ring.err, k0, h0, f0);
-            if (c) {
-                atomicAdd((unsigned long long *)c, (unsigned long long)c0);
-                last_key = k0;
-                last_pane = p0;
-                last_cnt = c;
-            }
-        }
-        if (n1) {
-            uint64_t *c = probe_resolve(
-                A.ring.keys + (size_t)p1 * A.ring.C,
-                A.ring.state + (size_t)p1 * A.ring.C * 2, A.ring.C,
-                A.ring.err, k1, h1, f1);
-            if (c) {
-                atomicAdd((unsigned long long *)c, (unsigned long long)c1);
-                last_key = k1;
-                last_pane = p1;
-                last_cnt = c;
-            }
-        }
-        if (Q == 4 && n2) {
-            uint64_t *c = probe_resolve(
-                A.ring.keys + (size_t)p2 * A.ring.C,
-                A.ring.state + (size_t)p2 * A.ring.C * 2, A.ring.C,
-                A.ring.err, k2, h2, f2);
-            if (c) {
-                atomicAdd((unsigned long long *)c, (unsigned long long)c2);
-                last_key = k2;
-                last_pane = p2;
-                last_cnt = c;
-            }
-        }
-        if (Q == 4 && n3) {
-            uint64_t *c = probe_resolve(
-                A.ring.keys + (size_t)p3 * A.ring.C,
-                A.ring.state + (size_t)p3 * A.ring.C * 2, A.ring.C,
-                A.ring.err, k3, h3, f3);
-            if (c) {
-                atomicAdd((unsigned long long *)c, (unsigned long long)c3);
-                last_key = k3;
-                last_pane = p3;
-                last_cnt = c;
-            }
-        }
-    }
-    /* tail rows (n_rows % Q) are handled by a separate scalar launch from
-     * the host: a device-side tail call forced caller-save scratch spills
-     * into this kernel's hot loop */
-    fold_min_bin(local_min, A.ring.min_bin);
-    /* flush the hot cache: <= BATCH_LSLOTS upserts per block */
-    __syncthreads();
-    for (int s = threadIdx.x; s < BATCH_LSLOTS; s += blockDim.x) {
-        int64_t key = ls_key[s];
-        if (key == EMPTY_KEY) continue;
-        uint32_t p = ls_pane[s];
-        uint64_t h = hash64((uint64_t)key) & m;
-        int64_t kk = A.ring.keys[(size_t)p * A.ring.C + h];
-        uint64_t *c = probe_resolve(A.ring.keys + (size_t)p * A.ring.C,
-                                    A.ring.state + (size_t)p * A.ring.C * 2,
-                                    A.ring.C, A.ring.err, key, h, kk);
-        if (c) atomicAdd((unsigned long long *)c, ls_cnt[s]);
-    }
-}
-
-template __global__ void k_update_batch<2>(UpdateArgs);
-template __global__ void k_update_batch<4>(UpdateArgs);
-
-/* array/loop form of the same kernel for wider quads (Q = 8): with the
- * helpers taking primitive arguments the ICE that forced the longhand
- * form above does not trigger.  87% of the narrow kernel's wave time is
- * parked on memory waits (SQ_WAIT_ANY, profiles/r02e) — wider quads put
- * more independent probe loads in flight per thread. */
+/* Q rows per thread per iteration (8, 12 or 16).  87% of the wave time of
+ * the narrow (Q = 2, 4) forms this replaced was parked on memory waits
+ * (SQ_WAIT_ANY, profiles/r02e) — wider groups put more independent probe
+ * loads in flight per thread.  The last n_rows % Q rows are left to a
+ * separate scalar launch from the host: a device-side tail call forced
+ * caller-save scratch spills into the hot loop. */
 template <int Q>
 __global__ void __launch_bounds__(256)
 k_update_batch_n(UpdateArgs A) {
@@ -1222,7 +795,7 @@ template __global__ void k_update_batch_n<12>(UpdateArgs);
 template __global__ void k_update_batch_n<16>(UpdateArgs);
 
 /* ------------------------------------------------------------------ */
-/* Tile update kernel (upd_kind 5, the default for the keyed single-COUNT
+/* Tile update kernel (UPD_TILE, the default for the keyed single-COUNT
  * shape).  A time-ordered stream is local: all occurrences of a nexmark
  * cold key fall inside one ~1.5K-row stretch of the input, so a block that
  * owns a CONTIGUOUS span of rows sees every occurrence of most of its keys.
@@ -1397,158 +970,7 @@ template __global__ void k_update_tile<12, TILE_SLOTS, TILE_PROBES>(UpdateArgs,
 template __global__ void k_update_tile<16, TILE_SLOTS, TILE_PROBES>(UpdateArgs,
                                                                     int);
 
-/* ------------------------------------------------------------------ */
-/* Radix-regroup update path (upd_kind 4).  The batched kernel is bound
- * by random-access THROUGHPUT: ~50 MB/launch of 64B-granule table RMWs
- * (cold keys have no block-local reuse — their ~7 occurrences land in
- * different blocks).  This path converts that into streaming:
- *   pass 1  histogram rows into 1024 hash-buckets, per (bucket, block)
- *   scan    exclusive sum (hipCUB) -> every block's private output range
- *   pass 2  scatter (key, pane) to bucket segments — LDS cursors only,
- *           no global atomics
- *   pass 3  one block per bucket aggregates its segment in LDS with
- *           EXCLUSIVE ownership of its keys, then writes each distinct
- *           (key, pane) once to the pane table
- * Round 1 tried a 256-bucket version and measured 6x slower; the fixes
- * here: 1024 buckets (the changing hot key spreads over ~1200 distinct
- * keys per launch, so buckets stay balanced), per-(bucket,block)
- * reservations instead of global scatter cursors, and the aggregation
- * table sized so a bucket's ~130 distinct keys never overflow. */
-#define RDX2_LOG_B 10
-#define RDX2_B (1u << RDX2_LOG_B)
-#define RDX2_HB 1024               /* hist/scatter grid blocks */
-#define RDX2_ASLOTS 2048           /* aggregation LDS slots per bucket */
-
-struct Rdx2Args {
-    const int64_t *key_col;
-    const int64_t *ts_col;
-    int64_t n_rows;
-    uint64_t slide, slide_inv;
-    uint64_t wm_bin;
-    int has_wm;
-    uint64_t ts_offset;
-    DeviceRing ring;
-    uint32_t *hist;       /* [RDX2_B * RDX2_HB + 1] */
-    int64_t *skey;        /* [cap] scatter output */
-    uint32_t *spane;      /* [cap] */
-};
-
-__global__ void __launch_bounds__(256)
-k_rdx2_hist(Rdx2Args A) {
-    __shared__ uint32_t cnt[RDX2_B];
-    for (int i = threadIdx.x; i < (int)RDX2_B; i += blockDim.x) cnt[i] = 0;
-    __syncthreads();
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    uint64_t local_min = ~0ULL, last_bin = EMPTY_TAG;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-         i < A.n_rows; i += stride) {
-        uint64_t t = (uint64_t)A.ts_col[i] + A.ts_offset;
-        uint64_t q = div_slide(t, A.slide, A.slide_inv);
-        uint64_t bin = q * A.slide;
-        if (A.has_wm && bin < A.wm_bin) continue;
-        if (bin < local_min) local_min = bin;
-        uint32_t p = (uint32_t)(q & (A.ring.R - 1));
-        if (bin != last_bin) {
-            claim_tag_wave(A.ring.tag, p, bin, EMPTY_TAG, A.ring.err);
-            last_bin = bin;
-        }
-        int64_t key = A.key_col[i];
-        if (key == EMPTY_KEY) {   /* sentinel: handled here, not scattered */
-            atomicExch(&A.ring.spec_used[p], 1u);
-            atomicAdd((unsigned long long *)
-                          (A.ring.spec_state + (size_t)p * 2), 1ULL);
-            continue;
-        }
-        atomicAdd(&cnt[(uint32_t)(hash64((uint64_t)key) >>
-                                  (64 - RDX2_LOG_B))], 1u);
-    }
-    fold_min_bin(local_min, A.ring.min_bin);
-    __syncthreads();
-    for (int i = threadIdx.x; i < (int)RDX2_B; i += blockDim.x)
-        A.hist[(size_t)i * RDX2_HB + blockIdx.x] = cnt[i];
-}
-
-__global__ void __launch_bounds__(256)
-k_rdx2_scatter(Rdx2Args A) {
-    __shared__ uint32_t cur[RDX2_B];
-    for (int i = threadIdx.x; i < (int)RDX2_B; i += blockDim.x)
-        cur[i] = A.hist[(size_t)i * RDX2_HB + blockIdx.x];
-    __syncthreads();
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-         i < A.n_rows; i += stride) {
-        uint64_t t = (uint64_t)A.ts_col[i] + A.ts_offset;
-        uint64_t q = div_slide(t, A.slide, A.slide_inv);
-        uint64_t bin = q * A.slide;
-        if (A.has_wm && bin < A.wm_bin) continue;
-        int64_t key = A.key_col[i];
-        if (key == EMPTY_KEY) continue;
-        uint32_t b = (uint32_t)(hash64((uint64_t)key) >> (64 - RDX2_LOG_B));
-        uint32_t pos = atomicAdd(&cur[b], 1u);
-        A.skey[pos] = key;
-        A.spane[pos] = (uint32_t)(q & (A.ring.R - 1));
-    }
-}
-
-__global__ void __launch_bounds__(256)
-k_rdx2_agg(Rdx2Args A) {
-    __shared__ int64_t lkey[RDX2_ASLOTS];
-    __shared__ uint32_t lpane[RDX2_ASLOTS];
-    __shared__ unsigned long long lcnt[RDX2_ASLOTS];
-    for (int i = threadIdx.x; i < RDX2_ASLOTS; i += blockDim.x) {
-        lkey[i] = EMPTY_KEY;
-        lpane[i] = PANE_UNSET;
-        lcnt[i] = 0;
-    }
-    __syncthreads();
-    uint32_t b = blockIdx.x;             /* gridDim.x == RDX2_B */
-    int64_t lo = A.hist[(size_t)b * RDX2_HB];
-    int64_t hi = A.hist[(size_t)(b + 1) * RDX2_HB];
-    for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-        int64_t key = A.skey[i];
-        uint32_t p = A.spane[i];
-        uint32_t h = (uint32_t)hash64((uint64_t)key * 0x9e3779b1u + p) &
-                     (RDX2_ASLOTS - 1);
-        for (int pr = 0; pr < RDX2_ASLOTS; pr++) {
-            uint32_t s = (h + pr) & (RDX2_ASLOTS - 1);
-            int64_t k = lkey[s];
-            bool claimed = false;
-            if (k == EMPTY_KEY) {
-                int64_t old = (int64_t)atomicCAS(
-                    (unsigned long long *)&lkey[s],
-                    (unsigned long long)EMPTY_KEY, (unsigned long long)key);
-                if (old == EMPTY_KEY) {
-                    lpane[s] = p;
-                    claimed = true;
-                    k = key;
-                } else {
-                    k = old;
-                }
-            }
-            if (k == key && (claimed || lpane[s] == p)) {
-                atomicAdd(&lcnt[s], 1ULL);
-                h = ~0u;   /* found */
-                break;
-            }
-        }
-        if (h != ~0u) *A.ring.err = ERR_TABLE_FULL;  /* bucket overflow */
-    }
-    __syncthreads();
-    /* exclusive ownership: each distinct (key, pane) written once */
-    for (int s = threadIdx.x; s < RDX2_ASLOTS; s += blockDim.x) {
-        int64_t key = lkey[s];
-        if (key == EMPTY_KEY) continue;
-        uint32_t p = lpane[s];
-        uint64_t h = hash64((uint64_t)key) & (A.ring.C - 1);
-        int64_t kk = A.ring.keys[(size_t)p * A.ring.C + h];
-        uint64_t *c = probe_resolve(A.ring.keys + (size_t)p * A.ring.C,
-                                    A.ring.state + (size_t)p * A.ring.C * 2,
-                                    A.ring.C, A.ring.err, key, h, kk);
-        if (c) atomicAdd((unsigned long long *)c, lcnt[s]);
-    }
-}
-
-/* scalar fallback of the batch kind (misaligned column pointers) */
+/* scalar kernel of the batch and tile kinds (tail rows, misaligned columns) */
 __global__ void __launch_bounds__(256)
 k_update_batch_scalar(UpdateArgs A) {
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -1594,21 +1016,7 @@ __global__ void k_retire_tags(RetireTagsArgs A) {
     }
 }
 
-/* packed pane clear: {EMPTY_KEY, 0} per slot (a single memset cannot set
- * the two words differently, and count must start at 0) */
-__global__ void __launch_bounds__(256)
-k_retire_packed(uint64_t *slots, int64_t n_slots) {
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-         i < n_slots; i += stride) {
-        ulonglong2 v;
-        v.x = (unsigned long long)EMPTY_KEY;
-        v.y = 0;
-        ((ulonglong2 *)slots)[i] = v;
-    }
-}
-
-/* one-launch pane retire for the split/unpacked layout: keys to 0xFF,
+/* one-launch pane retire (plane clears): keys to 0xFF,
  * states to 0, scalar metadata — replaces two fill launches plus a
  * metadata kernel (~5 us each on a busy stream) per retire */
 __global__ void __launch_bounds__(256)
@@ -1625,157 +1033,6 @@ k_retire_all(int64_t *keys, uint64_t *state, int64_t C, int na2) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
          i < sv2; i += stride)
         ((ulonglong2 *)state)[i] = zz;
-}
-
-/* ------------------------------------------------------------------ */
-/* Radix-partitioned update path (ARROYO_AMD_RADIX=1, keyed
- * n_value_cols==0 launches): instead of every block hammering the shared
- * pane tables, rows are first partitioned by the top 8 bits of hash(key)
- * (histogram -> exclusive scan -> scatter, all streaming), then ONE block
- * per bucket aggregates its rows -- every key belongs to exactly one
- * block, so the LDS table sees no cross-block duplication and the pane
- * table sees one uncontended upsert per distinct (key, bin) per launch.
- * Trades ~32 B/row of extra streaming traffic for the elimination of
- * cross-block atomic contention.                                      */
-#define RDX_BUCKETS 256
-#define RDX_SLOTS 4096           /* LDS table of the per-bucket aggregator */
-
-__global__ void __launch_bounds__(256)
-k_radix_hist(const int64_t *key_col, int64_t n_rows,
-             unsigned int *hist /* [RDX_BUCKETS][gridDim] */) {
-    __shared__ unsigned int cnt[RDX_BUCKETS];
-    for (int i = threadIdx.x; i < RDX_BUCKETS; i += blockDim.x) cnt[i] = 0;
-    __syncthreads();
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-         i < n_rows; i += stride)
-        atomicAdd(&cnt[hash64((uint64_t)key_col[i]) >> 56], 1u);
-    __syncthreads();
-    for (int i = threadIdx.x; i < RDX_BUCKETS; i += blockDim.x)
-        hist[(size_t)i * gridDim.x + blockIdx.x] = cnt[i];
-}
-
-__global__ void __launch_bounds__(256)
-k_radix_scatter(const int64_t *key_col, const int64_t *ts_col,
-                int64_t n_rows, uint64_t ts_offset,
-                const unsigned int *hist, int64_t *out_key,
-                int64_t *out_ts) {
-    __shared__ unsigned int cur[RDX_BUCKETS];
-    for (int i = threadIdx.x; i < RDX_BUCKETS; i += blockDim.x)
-        cur[i] = hist[(size_t)i * gridDim.x + blockIdx.x];
-    __syncthreads();
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-         i < n_rows; i += stride) {
-        int64_t k = key_col[i];
-        unsigned int pos = atomicAdd(&cur[hash64((uint64_t)k) >> 56], 1u);
-        out_key[pos] = k;
-        out_ts[pos] = ts_col[i] + (int64_t)ts_offset;
-    }
-}
-
-/* one block per bucket: rows [bstart, bend) of the scratch are this
- * block's exclusive key set */
-struct RadixAggArgs {
-    const int64_t *key;
-    const int64_t *ts;
-    const unsigned int *bucket_base;  /* hist after scan: [b][0] = start */
-    int hist_blocks;
-    int64_t n_rows;
-    uint64_t slide, slide_inv;
-    uint64_t wm_bin;
-    int has_wm;
-    DeviceRing ring;
-    AggSpec agg;
-};
-
-__global__ void __launch_bounds__(256)
-k_radix_agg(RadixAggArgs A) {
-    __shared__ int64_t  lkey[RDX_SLOTS];
-    __shared__ uint32_t lpane[RDX_SLOTS];
-    __shared__ uint64_t lcnt[RDX_SLOTS];   /* COUNT-only state (n_aggs==1) */
-    for (int i = threadIdx.x; i < RDX_SLOTS; i += blockDim.x) {
-        lkey[i] = EMPTY_KEY;
-        lpane[i] = PANE_UNSET;
-        lcnt[i] = 0;
-    }
-    __syncthreads();
-    int b = blockIdx.x;
-    int64_t lo = A.bucket_base[(size_t)b * A.hist_blocks];
-    int64_t hi = b + 1 < RDX_BUCKETS
-                     ? (int64_t)A.bucket_base[(size_t)(b + 1) * A.hist_blocks]
-                     : A.n_rows;
-    uint64_t local_min = ~0ULL, last_bin = EMPTY_TAG;
-    for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-        uint64_t t = (uint64_t)A.ts[i];
-        uint64_t q = div_slide(t, A.slide, A.slide_inv);
-        uint64_t bin = q * A.slide;
-        if (A.has_wm && bin < A.wm_bin) continue;
-        if (bin < local_min) local_min = bin;
-        uint32_t p = (uint32_t)(q & (A.ring.R - 1));
-        if (bin != last_bin) {
-            claim_tag_wave(A.ring.tag, p, bin, EMPTY_TAG, A.ring.err);
-            last_bin = bin;
-        }
-        int64_t key = A.key[i];
-        if (key == EMPTY_KEY) {
-            atomicExch(&A.ring.spec_used[p], 1u);
-            atomicAdd((unsigned long long *)
-                          &A.ring.spec_state[(size_t)p * A.agg.n_aggs * 2],
-                      1ULL);
-            continue;
-        }
-        uint32_t h = (uint32_t)hash64((uint64_t)key * 0x9e37u + p) &
-                     (RDX_SLOTS - 1);
-        bool done = false;
-        for (int pr = 0; pr < 8 && !done; pr++) {
-            uint32_t sl = (h + pr) & (RDX_SLOTS - 1);
-            int64_t k = lkey[sl];
-            bool claimed = false;
-            if (k == EMPTY_KEY) {
-                int64_t old = (int64_t)atomicCAS(
-                    (unsigned long long *)&lkey[sl],
-                    (unsigned long long)EMPTY_KEY, (unsigned long long)key);
-                if (old == EMPTY_KEY) {
-                    lpane[sl] = p;
-                    k = key;
-                    claimed = true;
-                } else {
-                    k = old;
-                }
-            }
-            if (k == key && (claimed || lpane[sl] == p)) {
-                atomicAdd((unsigned long long *)&lcnt[sl], 1ULL);
-                done = true;
-            }
-        }
-        if (!done) {
-            /* LDS full for this probe window: straight to the pane table
-             * (uncontended -- this block owns the key) */
-            int64_t *keys = A.ring.keys + (size_t)p * A.ring.C;
-            int64_t sl = table_upsert(keys, A.ring.C, key, A.ring.err);
-            if (sl >= 0)
-                atomicAdd((unsigned long long *)
-                              &A.ring.state[((size_t)p * A.ring.C +
-                                             (size_t)sl) *
-                                            A.agg.n_aggs * 2],
-                          1ULL);
-        }
-    }
-    fold_min_bin(local_min, A.ring.min_bin);
-    __syncthreads();
-    for (int i = threadIdx.x; i < RDX_SLOTS; i += blockDim.x) {
-        int64_t key = lkey[i];
-        if (key == EMPTY_KEY) continue;
-        uint32_t p = lpane[i];
-        int64_t *keys = A.ring.keys + (size_t)p * A.ring.C;
-        int64_t sl = table_upsert(keys, A.ring.C, key, A.ring.err);
-        if (sl < 0) continue;
-        atomicAdd((unsigned long long *)
-                      &A.ring.state[((size_t)p * A.ring.C + (size_t)sl) *
-                                    A.agg.n_aggs * 2],
-                  (unsigned long long)lcnt[i]);
-    }
 }
 
 /* ------------------------------------------------------------------ */
@@ -1925,18 +1182,6 @@ k_merge(MergeArgs M) {
          i < total; i += stride) {
         uint32_t p = M.src[i / M.ring.C];
         size_t slot = i % M.ring.C;
-        if (M.ring.packed) {
-            const uint64_t *s =
-                M.ring.slots + ((size_t)p * M.ring.C + slot) * 2;
-            int64_t key = (int64_t)s[0];
-            if (key == EMPTY_KEY) continue;
-            int64_t d = table_upsert(M.m_keys, M.CM, key, M.ring.err);
-            if (d < 0) continue;
-            uint64_t src_state[2] = {s[1], 0};
-            atomic_merge(M.m_state + (size_t)d * M.agg.n_aggs * 2,
-                         src_state, M.agg);
-            continue;
-        }
         int64_t key = M.ring.keys[(size_t)p * M.ring.C + slot];
         if (key == EMPTY_KEY) continue;
         int64_t d = table_upsert(M.m_keys, M.CM, key, M.ring.err);
@@ -2182,7 +1427,7 @@ k_cpi_build(CpiBuildArgs A) {
     if (threadIdx.x == 0) A.cnt[blockIdx.x] = lcur < A.range ? lcur : A.range;
 }
 
-template <int SLOTS, bool PACKED = false>
+template <int SLOTS>
 __global__ void __launch_bounds__(256)
 k_merge_fused(MergeFusedArgs M) {
     __shared__ int64_t lkey[SLOTS];
@@ -2194,7 +1439,7 @@ k_merge_fused(MergeFusedArgs M) {
     __shared__ unsigned long long blk_base;
     __shared__ unsigned int blk_cnt;
     const int na = M.agg.n_aggs;
-    const int compact = (!PACKED && M.use_cpi && M.cpi_ew == 2);
+    const int compact = (M.use_cpi && M.cpi_ew == 2);
     const int sw = compact ? 1 : na * 2;
     const uint32_t C = M.ring.C, mask = C - 1;
     for (int i = threadIdx.x; i < SLOTS; i += blockDim.x) {
@@ -2206,14 +1451,9 @@ k_merge_fused(MergeFusedArgs M) {
     uint32_t a = blockIdx.x * M.range;           /* gridDim.x == C/range */
     uint32_t span = M.range + MAX_PROBES;        /* displacement overscan */
     for (int p = 0; p < M.n_src; p++) {
-        const int64_t *keys =
-            PACKED ? nullptr : M.ring.keys + (size_t)M.src[p] * C;
-        const uint64_t *st =
-            PACKED ? nullptr : M.ring.state + (size_t)M.src[p] * C * na * 2;
-        const uint64_t *pslots =
-            PACKED ? M.ring.slots + (size_t)M.src[p] * C * 2 : nullptr;
-        auto fold = [&](int64_t key, const uint64_t *stv, uint64_t pw0,
-                        bool own) {
+        const int64_t *keys = M.ring.keys + (size_t)M.src[p] * C;
+        const uint64_t *st = M.ring.state + (size_t)M.src[p] * C * na * 2;
+        auto fold = [&](int64_t key, const uint64_t *stv, bool own) {
             if (key == EMPTY_KEY) return;
             if (!own) {
                 uint32_t rel = ((uint32_t)hash64((uint64_t)key) - a) & mask;
@@ -2238,11 +1478,6 @@ k_merge_fused(MergeFusedArgs M) {
             }
             if (slot < 0) { *M.ring.err = ERR_MF_OVERFLOW; return; }
             uint64_t *d = lst + (size_t)slot * sw;
-            if (PACKED) {   /* single COUNT state, read with the key */
-                atomicAdd((unsigned long long *)&d[0],
-                          (unsigned long long)pw0);
-                return;
-            }
             if (compact) {   /* single live word: fold without the pair
                                 stride atomic_merge assumes */
                 switch (M.agg.op[0]) {
@@ -2264,7 +1499,7 @@ k_merge_fused(MergeFusedArgs M) {
             }
             atomic_merge(d, stv, M.agg);
         };
-        if (!PACKED && M.use_cpi) {
+        if (M.use_cpi) {
             /* dense home-range-grouped entries: only occupied slots read,
              * ownership established at build time */
             const int ew = M.cpi_ew;
@@ -2290,29 +1525,23 @@ k_merge_fused(MergeFusedArgs M) {
                         ulonglong2 e3 =
                             ((const ulonglong2 *)ent)[t + 3 * stride];
                         uint64_t w;
-                        w = e0.y; fold((int64_t)e0.x, &w, 0, true);
-                        w = e1.y; fold((int64_t)e1.x, &w, 0, true);
-                        w = e2.y; fold((int64_t)e2.x, &w, 0, true);
-                        w = e3.y; fold((int64_t)e3.x, &w, 0, true);
+                        w = e0.y; fold((int64_t)e0.x, &w, true);
+                        w = e1.y; fold((int64_t)e1.x, &w, true);
+                        w = e2.y; fold((int64_t)e2.x, &w, true);
+                        w = e3.y; fold((int64_t)e3.x, &w, true);
                     }
                     for (; t < n_e; t += stride) {
                         ulonglong2 e = ((const ulonglong2 *)ent)[t];
                         uint64_t w0 = (uint64_t)e.y;
-                        fold((int64_t)e.x, &w0, 0, true);
+                        fold((int64_t)e.x, &w0, true);
                     }
                 } else {
                     for (uint32_t t = threadIdx.x; t < n_e;
                          t += blockDim.x) {
                         const uint64_t *e = ent + (size_t)t * ew;
-                        fold((int64_t)e[0], e + 1, 0, true);
+                        fold((int64_t)e[0], e + 1, true);
                     }
                 }
-            }
-        } else if (PACKED) {
-            for (uint32_t t = threadIdx.x; t < span; t += blockDim.x) {
-                uint32_t idx = (a + t) & mask;
-                ulonglong2 sv = ((const ulonglong2 *)pslots)[idx];
-                fold((int64_t)sv.x, nullptr, sv.y, false);
             }
         } else {
             /* 2 keys per 16 B load: a and span are multiples of 2, and an
@@ -2321,9 +1550,8 @@ k_merge_fused(MergeFusedArgs M) {
                  t += 2 * blockDim.x) {
                 uint32_t idx = (a + t) & mask;
                 ulonglong2 kv = *(const ulonglong2 *)&keys[idx];
-                fold((int64_t)kv.x, st + (size_t)idx * na * 2, 0, false);
-                fold((int64_t)kv.y, st + ((size_t)idx + 1) * na * 2, 0,
-                     false);
+                fold((int64_t)kv.x, st + (size_t)idx * na * 2, false);
+                fold((int64_t)kv.y, st + ((size_t)idx + 1) * na * 2, false);
             }
         }
     }
@@ -2597,8 +1825,6 @@ k_merge_dual(MergeDualArgs M) {
 }
 
 template __global__ void k_merge_dual<2048>(MergeDualArgs);
-template __global__ void k_merge_fused<1024, true>(MergeFusedArgs);
-template __global__ void k_merge_fused<2048, true>(MergeFusedArgs);
 
 /* restore checkpointed partial states: insert raw state rows into a pane. */
 struct RestoreArgs {
@@ -2631,14 +1857,6 @@ k_restore(RestoreArgs R) {
         if (key == EMPTY_KEY) {
             atomicExch(&R.ring.spec_used[p], 1u);
             st = R.ring.spec_state + (size_t)p * R.agg.n_aggs * 2;
-        } else if (R.ring.packed) {
-            uint64_t *c = packed_upsert(
-                R.ring.slots + (size_t)p * R.ring.C * 2, R.ring.C, key,
-                R.ring.err);
-            if (c)
-                atomicAdd((unsigned long long *)c,
-                          (unsigned long long)enc[0]);
-            continue;
         } else {
             int64_t *keys = R.ring.keys + (size_t)p * R.ring.C;
             int64_t s = table_upsert(keys, R.ring.C, key, R.ring.err);
@@ -2712,6 +1930,15 @@ struct Staged {
     int64_t  cap, n;
     int64_t *dbuf[16];
     int      ncols;
+};
+
+/* update kernel of an operator (ARROYO_AMD_UPD=lds|batch|tile) */
+enum UpdKind {
+    UPD_LDS,    /* k_update_lds_vec / k_update_lds: every shape; the only
+                   kind for anything but keyed single-COUNT */
+    UPD_BATCH,  /* k_update_batch_n: keyed single-COUNT, kept as the
+                   documented comparison for the tile kernel */
+    UPD_TILE,   /* k_update_tile: keyed single-COUNT, its default */
 };
 
 struct GpuOp {
@@ -2813,9 +2040,7 @@ struct GpuOp {
     std::map<uint64_t, uint32_t> closed;  /* bin -> ring slot (tiered) */
     std::set<uint64_t> table_bins;        /* ExpiringTimeKeyView keys */
 
-    int use_lds;
-    int upd_kind;   /* 0 lds, 1 packed AoS, 2 split wave-combine,
-                       3 batched-probe, 4 radix-regroup, 5 tile */
+    UpdKind upd_kind;
     /* closed-pane index (see CpiBuildArgs) */
     uint64_t *cpi_entries;      /* [R][NR][cpi_range][cpi_ew] */
     uint32_t *cpi_cnt;          /* [R][NR] */
@@ -2833,24 +2058,17 @@ struct GpuOp {
     int64_t *d_keyid_in;
     int64_t keyid_in_cap;
     int64_t *d_keyid_out;
-    int64_t *rdx2_skey;
-    uint32_t *rdx2_spane;
-    uint32_t *rdx2_hist;
-    void *rdx2_tmp;
-    size_t rdx2_tmp_bytes;
-    int64_t rdx2_cap;
-    int use_radix;             /* ARROYO_AMD_RADIX=1: partitioned update */
-    int64_t *rdx_key, *rdx_ts; /* scatter scratch (lazily sized) */
-    unsigned int *rdx_hist;
-    void *rdx_tmp;
-    size_t rdx_tmp_bytes;
-    int64_t rdx_cap;
-    int force_blocks;
-    int tile_resident = 0;    /* k_update_tile blocks the device holds at once */
-    int tile_resident_q = 0;  /* ... queried for this rows-per-thread */
-    int kmode;
-    int use_vec;
-    int use_wavecmb = 0;
+    /* update-launch knobs, read once at create */
+    int force_blocks;         /* ARROYO_AMD_BLOCKS: grid size, 0 = computed */
+    int bq;                   /* ARROYO_AMD_BQ: rows per thread per iteration
+                                 of the batch and tile kernels: 8, 12 or 16 */
+    int pblocks;              /* ARROYO_AMD_PBLOCKS: batch grid cap / tile
+                                 block budget */
+    int pblocks_set;          /* ... was given (else the tile budget is
+                                 tile_resident) */
+    int tile_s;               /* ARROYO_AMD_TILE_S: tile span, 0 = computed */
+    int tile_resident;        /* k_update_tile<bq> blocks the device holds at
+                                 once; queried at the first tile launch */
     int use_events;
     /* perf counters for bench; a fixed pool of reusable event pairs samples
      * a subset of launches (create/destroy per launch was host overhead) */
@@ -2944,18 +2162,10 @@ static int ring_retire_planes(GpuOp *o, uint32_t slot, uint64_t bin) {
     if (slot < o->retired_bin.size()) o->retired_bin[slot] = bin;
     int blocks = (int)((o->ring.C + 255) / 256);
     if (blocks > 1024) blocks = 1024;
-    if (o->ring.packed) {
-        hipLaunchKernelGGL(k_retire_packed, dim3(blocks), dim3(256), 0,
-                           o->fstream,
-                           o->ring.slots + (size_t)slot * o->ring.C * 2,
-                           (int64_t)o->ring.C);
-    } else {
-        hipLaunchKernelGGL(k_retire_all, dim3(blocks), dim3(256), 0,
-                           o->fstream,
-                           o->ring.keys + (size_t)slot * o->ring.C,
-                           o->ring.state + (size_t)slot * o->ring.C * na * 2,
-                           (int64_t)o->ring.C, (int)(na * 2));
-    }
+    hipLaunchKernelGGL(k_retire_all, dim3(blocks), dim3(256), 0, o->fstream,
+                       o->ring.keys + (size_t)slot * o->ring.C,
+                       o->ring.state + (size_t)slot * o->ring.C * na * 2,
+                       (int64_t)o->ring.C, (int)(na * 2));
     HIP_CHECK(o, hipGetLastError());
     o->retire_pend.push_back(slot);
     if ((int)o->retire_pend.size() >= 8) return ring_retire_flush(o);
@@ -3064,17 +2274,21 @@ API void *arroyo_amd_create(const AmdWindowConfig *cfg) {
     o->ring.R = cfg->ring_panes ? cfg->ring_panes : 64;
     o->CM = o->ring.C * 2;
     o->state = 0;
-    o->use_lds = 1;
-    if (const char *e = getenv("ARROYO_AMD_LDS")) o->use_lds = atoi(e);
-    o->use_radix = 0;
-    if (const char *e = getenv("ARROYO_AMD_RADIX")) o->use_radix = atoi(e);
     o->force_blocks = 0;
     if (const char *e = getenv("ARROYO_AMD_BLOCKS")) o->force_blocks = atoi(e);
-    o->kmode = 0;
-    if (const char *e = getenv("ARROYO_AMD_KMODE")) o->kmode = atoi(e);
-    o->use_vec = 1;
-    if (const char *e = getenv("ARROYO_AMD_VEC")) o->use_vec = atoi(e);
-    if (const char *e = getenv("ARROYO_AMD_WAVECMB")) o->use_wavecmb = atoi(e);
+    o->bq = 8;
+    if (const char *e = getenv("ARROYO_AMD_BQ")) o->bq = atoi(e);
+    o->bq = o->bq >= 16 ? 16 : o->bq >= 12 ? 12 : 8;
+    o->pblocks = 2048;
+    o->pblocks_set = 0;
+    if (const char *e = getenv("ARROYO_AMD_PBLOCKS")) {
+        o->pblocks = atoi(e);
+        o->pblocks_set = 1;
+    }
+    o->tile_s = 0;
+    if (const char *e = getenv("ARROYO_AMD_TILE_S"))
+        if (atoi(e) > 0) o->tile_s = atoi(e);
+    o->tile_resident = 0;
     o->use_events = 1;
     if (const char *e = getenv("ARROYO_AMD_EVENTS")) o->use_events = atoi(e);
 
@@ -3092,40 +2306,24 @@ API void *arroyo_amd_create(const AmdWindowConfig *cfg) {
         delete o;
         return nullptr;
     };
-    /* update-kernel flavor for the keyed single-COUNT shape (the q5
-     * headline): "split" = wave-combine no-LDS kernel over the standard
-     * split key/state arrays (default; key probes stay L2-clean),
-     * "packed" = the same kernel over an AoS {key,count} table,
-     * "lds" = the round-1 LDS-staged kernel (see k_update_packed),
-     * "batch" = k_update_batch_n, "tile" = k_update_tile (default). */
+    /* update kernel: the keyed single-COUNT shape (the q5 headline) takes
+     * the tile kernel by default and may be switched to "batch" or "lds";
+     * every other shape always takes the LDS-staged kernel.  An unknown
+     * value leaves the shape's default. */
     bool count_shape = (o->cfg.n_keys == 1 && o->agg.n_aggs == 1 &&
-                        o->agg.op[0] == AMD_AGG_COUNT && !o->use_radix &&
-                        o->kmode == 0);
-    o->upd_kind = count_shape ? 5 : 0;
+                        o->agg.op[0] == AMD_AGG_COUNT);
+    o->upd_kind = count_shape ? UPD_TILE : UPD_LDS;
     if (const char *ev = getenv("ARROYO_AMD_UPD")) {
-        if (!strcmp(ev, "lds")) o->upd_kind = 0;
-        else if (count_shape && !strcmp(ev, "packed")) o->upd_kind = 1;
-        else if (count_shape && !strcmp(ev, "split")) o->upd_kind = 2;
-        else if (count_shape && !strcmp(ev, "batch")) o->upd_kind = 3;
-        else if (count_shape && !strcmp(ev, "rdx2")) o->upd_kind = 4;
-        else if (count_shape && !strcmp(ev, "tile")) o->upd_kind = 5;
+        if (!strcmp(ev, "lds")) o->upd_kind = UPD_LDS;
+        else if (count_shape && !strcmp(ev, "batch")) o->upd_kind = UPD_BATCH;
+        else if (count_shape && !strcmp(ev, "tile")) o->upd_kind = UPD_TILE;
     }
-    if (const char *ev = getenv("ARROYO_AMD_PACKED"))   /* legacy alias */
-        if (!atoi(ev)) o->upd_kind = 0;
-    o->ring.packed = o->upd_kind == 1;
     hipError_t e;
 #define ALLOC(p, bytes)                                                      \
     if ((e = hipMalloc((void **)&(p), (bytes))) != hipSuccess)               \
         return fail(#p, e);
-    if (o->ring.packed) {
-        ALLOC(o->ring.slots, (size_t)o->ring.R * o->ring.C * 16);
-        o->ring.keys = nullptr;
-        o->ring.state = nullptr;
-    } else {
-        ALLOC(o->ring.keys, (size_t)o->ring.R * o->ring.C * 8);
-        ALLOC(o->ring.state, (size_t)o->ring.R * o->ring.C * na * 16);
-        o->ring.slots = nullptr;
-    }
+    ALLOC(o->ring.keys, (size_t)o->ring.R * o->ring.C * 8);
+    ALLOC(o->ring.state, (size_t)o->ring.R * o->ring.C * na * 16);
     ALLOC(o->d_status, (2 + (size_t)o->ring.R) * 8);
     o->ring.err = (int *)o->d_status;
     o->ring.min_bin = o->d_status + 1;
@@ -3172,7 +2370,7 @@ API void *arroyo_amd_create(const AmdWindowConfig *cfg) {
             o->cpi_range &= o->cpi_range - 1;
     }
     o->cpi_nr = o->ring.C / o->cpi_range;
-    if (!o->ring.packed && na <= MF_MAX_AGGS && !o->cfg.is_tumbling &&
+    if (na <= MF_MAX_AGGS && !o->cfg.is_tumbling &&
         o->cpi_nr <= CPI_MAX_NR) {
         int use_cpi = 1;
         if (const char *ev = getenv("ARROYO_AMD_CPI")) use_cpi = atoi(ev);
@@ -3198,14 +2396,8 @@ API void *arroyo_amd_create(const AmdWindowConfig *cfg) {
         hipMemset(o->d_dict_ready, 0, (size_t)o->dict_D * 4);
     }
 #undef ALLOC
-    if (o->ring.packed) {
-        int64_t n_slots = (int64_t)o->ring.R * o->ring.C;
-        hipLaunchKernelGGL(k_retire_packed, dim3(1024), dim3(256), 0, 0,
-                           o->ring.slots, n_slots);
-    } else {
-        hipMemset(o->ring.keys, 0xFF, (size_t)o->ring.R * o->ring.C * 8);
-        hipMemset(o->ring.state, 0, (size_t)o->ring.R * o->ring.C * na * 16);
-    }
+    hipMemset(o->ring.keys, 0xFF, (size_t)o->ring.R * o->ring.C * 8);
+    hipMemset(o->ring.state, 0, (size_t)o->ring.R * o->ring.C * na * 16);
     hipMemset(o->ring.tag, 0xFF, (size_t)o->ring.R * 8);
     hipMemset(o->ring.spec_used, 0, (size_t)o->ring.R * 4);
     hipMemset(o->ring.spec_state, 0, (size_t)o->ring.R * na * 16);
@@ -3297,59 +2489,108 @@ API const char *arroyo_amd_last_error(void *h) {
     return h ? ((GpuOp *)h)->err_msg : g_err;
 }
 
-#define RDX_HIST_BLOCKS 640
+/* 16 B vector loads need a row pair and 16 B-aligned ts/key columns */
+static bool cols_vec_ok(const UpdateArgs &A) {
+    return A.n_rows >= 2 && ((uintptr_t)A.ts_col & 15) == 0 &&
+           ((uintptr_t)A.key_col & 15) == 0;   /* null (unkeyed) passes */
+}
 
-static int launch_update_radix(GpuOp *o, const int64_t *key_col,
-                               const int64_t *ts_col, int64_t n_rows,
-                               uint64_t ts_offset) {
-    if (n_rows > o->rdx_cap) {
-        hipFree(o->rdx_key);
-        hipFree(o->rdx_ts);
-        hipFree(o->rdx_hist);
-        hipFree(o->rdx_tmp);
-        o->rdx_cap = n_rows + (n_rows >> 2);
-        HIP_CHECK(o, hipMalloc((void **)&o->rdx_key,
-                               (size_t)o->rdx_cap * 8));
-        HIP_CHECK(o, hipMalloc((void **)&o->rdx_ts,
-                               (size_t)o->rdx_cap * 8));
-        HIP_CHECK(o, hipMalloc((void **)&o->rdx_hist,
-                               (size_t)RDX_BUCKETS * RDX_HIST_BLOCKS * 4));
-        o->rdx_tmp_bytes = 0;
-        hipcub::DeviceScan::ExclusiveSum(
-            nullptr, o->rdx_tmp_bytes, o->rdx_hist, o->rdx_hist,
-            RDX_BUCKETS * RDX_HIST_BLOCKS);
-        HIP_CHECK(o, hipMalloc(&o->rdx_tmp,
-                               o->rdx_tmp_bytes ? o->rdx_tmp_bytes : 1));
+/* UPD_LDS: two rows per thread when the columns allow it, else one */
+static void launch_lds(GpuOp *o, const UpdateArgs &A) {
+    bool vec = cols_vec_ok(A);
+    int64_t units = vec ? (A.n_rows + 1) / 2 : A.n_rows;
+    int64_t want = (units + 255) / 256;
+    /* grid-sweep optima: 640 blocks at ~0.5M units (1M-row launches), 896
+     * at ~1M units (2M-row fused launches).  Fewer blocks -> fewer
+     * same-key flush contenders on the global table; more -> better tail
+     * occupancy at larger launches. */
+    int cap = units >= (640 << 10) ? 896 : 640;
+    int blocks = (int)(want > cap ? cap : (want < 1 ? 1 : want));
+    if (o->force_blocks > 0) blocks = o->force_blocks;
+    size_t shmem = (size_t)LDS_SLOTS * o->agg.n_aggs * 16;
+    bool count_only = o->agg.n_aggs == 1 && o->agg.op[0] == AMD_AGG_COUNT;
+    if (!vec)
+        hipLaunchKernelGGL(k_update_lds, dim3(blocks), dim3(256), shmem,
+                           o->stream, A);
+    else if (count_only)
+        hipLaunchKernelGGL((k_update_lds_vec<LDS_SLOTS, true>), dim3(blocks),
+                           dim3(256), shmem, o->stream, A);
+    else
+        hipLaunchKernelGGL((k_update_lds_vec<LDS_SLOTS, false>), dim3(blocks),
+                           dim3(256), shmem, o->stream, A);
+}
+
+/* the batch and tile kernels skip the last n_rows % bq rows; finish them
+ * with a tiny scalar launch (same parity) */
+static void launch_batch_tail(GpuOp *o, const UpdateArgs &A) {
+    int64_t tail = A.n_rows % o->bq;
+    if (!tail) return;
+    UpdateArgs T = A;
+    T.key_col = A.key_col + (A.n_rows - tail);
+    T.ts_col = A.ts_col + (A.n_rows - tail);
+    T.n_rows = tail;
+    hipLaunchKernelGGL(k_update_batch_scalar, dim3(1), dim3(64), 0, o->stream,
+                       T);
+}
+
+/* UPD_BATCH: grid-stride k_update_batch_n<bq>; the scalar kernel when the
+ * columns cannot be vector-loaded (UPD_TILE shares that fallback) */
+static void launch_batch(GpuOp *o, const UpdateArgs &A) {
+    bool vec = cols_vec_ok(A);
+    int64_t units = vec ? (A.n_rows + 1) / 4 : A.n_rows;
+    int64_t want = (units + 255) / 256;
+    int blocks = (int)(want > o->pblocks ? o->pblocks : (want < 1 ? 1 : want));
+    if (o->force_blocks > 0) blocks = o->force_blocks;
+    if (!vec) {
+        hipLaunchKernelGGL(k_update_batch_scalar, dim3(blocks), dim3(256), 0,
+                           o->stream, A);
+        return;
     }
-    hipLaunchKernelGGL(k_radix_hist, dim3(RDX_HIST_BLOCKS), dim3(256), 0,
-                       o->stream, key_col, n_rows, o->rdx_hist);
-    HIP_CHECK(o, hipGetLastError());
-    size_t tmp = o->rdx_tmp_bytes;
-    hipcub::DeviceScan::ExclusiveSum(o->rdx_tmp, tmp, o->rdx_hist,
-                                     o->rdx_hist,
-                                     RDX_BUCKETS * RDX_HIST_BLOCKS,
-                                     o->stream);
-    hipLaunchKernelGGL(k_radix_scatter, dim3(RDX_HIST_BLOCKS), dim3(256), 0,
-                       o->stream, key_col, ts_col, n_rows, ts_offset,
-                       o->rdx_hist, o->rdx_key, o->rdx_ts);
-    HIP_CHECK(o, hipGetLastError());
-    RadixAggArgs A = {};
-    A.key = o->rdx_key;
-    A.ts = o->rdx_ts;
-    A.bucket_base = o->rdx_hist;
-    A.hist_blocks = RDX_HIST_BLOCKS;
-    A.n_rows = n_rows;
-    A.slide = o->slide;
-    A.slide_inv = o->slide == 1
-                      ? ~0ULL
-                      : (uint64_t)((((unsigned __int128)1) << 64) / o->slide);
-    A.wm_bin = o->has_wm ? o->wm - o->wm % o->slide : 0;
-    A.has_wm = o->has_wm;
-    A.ring = o->ring;
-    A.agg = o->agg;
-    hipLaunchKernelGGL(k_radix_agg, dim3(RDX_BUCKETS), dim3(256), 0,
-                       o->stream, A);
-    HIP_CHECK(o, hipGetLastError());
+    auto kern = k_update_batch_n<8>;
+    if (o->bq == 16) kern = k_update_batch_n<16>;
+    else if (o->bq == 12) kern = k_update_batch_n<12>;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, o->stream, A);
+    launch_batch_tail(o, A);
+}
+
+/* UPD_TILE: contiguous spans: block b owns sub-tiles [b*S, (b+1)*S) of
+ * 256*bq rows.  The block budget only sets the span length, so locality
+ * never depends on a grid cap.  By default the budget is the number of
+ * blocks the device holds at once: a launch that fits keeps one sub-tile
+ * per block, a larger one grows the span until the grid is a single
+ * resident wave (measured best at the bench's 3.5M-row launches: S=2,
+ * profiles/tile_update_note.md).  PBLOCKS or a forced block count replace
+ * the budget, TILE_S the span itself. */
+static int launch_tile(GpuOp *o, const UpdateArgs &A) {
+    if (!cols_vec_ok(A)) {
+        launch_batch(o, A);
+        return 0;
+    }
+    auto kern = k_update_tile<8, TILE_SLOTS, TILE_PROBES>;
+    if (o->bq == 16) kern = k_update_tile<16, TILE_SLOTS, TILE_PROBES>;
+    else if (o->bq == 12) kern = k_update_tile<12, TILE_SLOTS, TILE_PROBES>;
+    if (!o->tile_resident) {
+        int per_cu = 0, cus = 0;
+        hipError_t e1 = hipOccupancyMaxActiveBlocksPerMultiprocessor(
+            &per_cu, kern, 256, 0);
+        hipError_t e2 = hipDeviceGetAttribute(
+            &cus, hipDeviceAttributeMultiprocessorCount, o->cfg.device);
+        HIP_CHECK(o, e1);
+        HIP_CHECK(o, e2);
+        o->tile_resident = per_cu * cus > 0 ? per_cu * cus : 1;
+    }
+    int64_t tiles = (A.n_rows / o->bq + 255) / 256;
+    if (tiles < 1) tiles = 1;
+    int64_t budget = o->tile_resident;
+    if (o->pblocks_set) budget = o->pblocks;
+    if (o->force_blocks > 0) budget = o->force_blocks;
+    if (budget < 1) budget = 1;
+    int64_t span = (tiles + budget - 1) / budget;
+    if (o->tile_s > 0) span = o->tile_s;
+    int blocks = (int)((tiles + span - 1) / span);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, o->stream, A,
+                       (int)span);
+    launch_batch_tail(o, A);
     return 0;
 }
 
@@ -3372,20 +2613,6 @@ static int launch_update(GpuOp *o, const int64_t *const *dcols, int64_t n_rows,
     A.ts_offset = ts_offset;
     A.ring = o->ring;
     A.agg = o->agg;
-    A.mode = o->kmode;
-    /* vectorized path needs 16B-aligned ts/key columns */
-    bool vec = o->use_lds && o->use_vec && n_rows >= 2 &&
-               ((uintptr_t)A.ts_col & 15) == 0 &&
-               (!A.key_col || ((uintptr_t)A.key_col & 15) == 0);
-    int64_t units = vec ? (n_rows + 1) / 2 : n_rows;
-    int64_t want = (units + 255) / 256;
-    /* grid-sweep optima: 640 blocks at ~0.5M units (1M-row launches), 896
-     * at ~1M units (2M-row fused launches).  Fewer blocks -> fewer
-     * same-key flush contenders on the global table; more -> better tail
-     * occupancy at larger launches. */
-    int cap = units >= (640 << 10) ? 896 : 640;
-    int blocks = (int)(want > cap ? cap : (want < 1 ? 1 : want));
-    if (o->force_blocks > 0) blocks = o->force_blocks;
     /* sample kernel time on a subset of launches via a reusable event pool */
     bool sample = o->use_events && (o->launches & 7) == 0;
     if (sample && o->ev_pool.empty()) {
@@ -3403,216 +2630,12 @@ static int launch_update(GpuOp *o, const int64_t *const *dcols, int64_t n_rows,
         ev = (int)(o->ev_inflight.size());
         hipEventRecord(o->ev_pool[ev].first, o->stream);
     }
-    if (o->upd_kind == 4) {
-        if (n_rows > o->rdx2_cap) {
-            hipFree(o->cpi_entries);
-    hipFree(o->cpi_cnt);
-    hipFree(o->d_dict_digest);
-    hipFree(o->d_dict_keys);
-    hipFree(o->d_dict_ready);
-    hipFree(o->d_keyid_in);
-    hipFree(o->d_keyid_out);
-    hipFree(o->rdx2_skey);
-            hipFree(o->rdx2_spane);
-            o->rdx2_cap = n_rows + (n_rows >> 2);
-            HIP_CHECK(o, hipMalloc((void **)&o->rdx2_skey,
-                                   (size_t)o->rdx2_cap * 8));
-            HIP_CHECK(o, hipMalloc((void **)&o->rdx2_spane,
-                                   (size_t)o->rdx2_cap * 4));
-            if (!o->rdx2_hist) {
-                HIP_CHECK(o, hipMalloc((void **)&o->rdx2_hist,
-                                       ((size_t)RDX2_B * RDX2_HB + 1) * 4));
-                o->rdx2_tmp_bytes = 0;
-                hipcub::DeviceScan::ExclusiveSum(
-                    nullptr, o->rdx2_tmp_bytes, o->rdx2_hist, o->rdx2_hist,
-                    RDX2_B * RDX2_HB + 1);
-                HIP_CHECK(o, hipMalloc(&o->rdx2_tmp,
-                                       o->rdx2_tmp_bytes ? o->rdx2_tmp_bytes
-                                                         : 1));
-            }
-        }
-        Rdx2Args R = {};
-        R.key_col = A.key_col;
-        R.ts_col = A.ts_col;
-        R.n_rows = n_rows;
-        R.slide = A.slide;
-        R.slide_inv = A.slide_inv;
-        R.wm_bin = A.wm_bin;
-        R.has_wm = A.has_wm;
-        R.ts_offset = A.ts_offset;
-        R.ring = o->ring;
-        R.hist = o->rdx2_hist;
-        R.skey = o->rdx2_skey;
-        R.spane = o->rdx2_spane;
-        HIP_CHECK(o, hipMemsetAsync(o->rdx2_hist + (size_t)RDX2_B * RDX2_HB,
-                                    0, 4, o->stream));
-        hipLaunchKernelGGL(k_rdx2_hist, dim3(RDX2_HB), dim3(256), 0,
-                           o->stream, R);
-        size_t tmp = o->rdx2_tmp_bytes;
-        hipcub::DeviceScan::ExclusiveSum(o->rdx2_tmp, tmp, o->rdx2_hist,
-                                         o->rdx2_hist, RDX2_B * RDX2_HB + 1,
-                                         o->stream);
-        hipLaunchKernelGGL(k_rdx2_scatter, dim3(RDX2_HB), dim3(256), 0,
-                           o->stream, R);
-        hipLaunchKernelGGL(k_rdx2_agg, dim3(RDX2_B), dim3(256), 0,
-                           o->stream, R);
-        HIP_CHECK(o, hipGetLastError());
-        if (sample) {
-            hipEventRecord(o->ev_pool[ev].second, o->stream);
-            o->ev_inflight.push_back(ev);
-        }
-        o->update_rows += n_rows;
-        o->launches++;
-        return 0;
-    }
-    if (o->upd_kind != 0) {
-        bool pvec = n_rows >= 2 && ((uintptr_t)A.ts_col & 15) == 0 &&
-                    ((uintptr_t)A.key_col & 15) == 0;
-        bool batched = o->upd_kind == 3 || o->upd_kind == 5;
-        int64_t punits = pvec ? (n_rows + 1) / (batched ? 4 : 2) : n_rows;
-        int64_t pwant = (punits + 255) / 256;
-        int pcap = 2048;
-        if (const char *ev2 = getenv("ARROYO_AMD_PBLOCKS")) pcap = atoi(ev2);
-        int pblocks = (int)(pwant > pcap ? pcap : (pwant < 1 ? 1 : pwant));
-        if (o->force_blocks > 0) pblocks = o->force_blocks;
-        if (batched) {
-            int bq = 8;
-            if (const char *ev3 = getenv("ARROYO_AMD_BQ")) bq = atoi(ev3);
-            if (!pvec) bq = 1;
-            /* the row count each kernel thread takes per iteration */
-            bq = bq >= 16 ? 16 : bq >= 12 ? 12 : bq >= 8 ? 8
-               : bq >= 4 ? 4 : bq >= 2 ? 2 : 1;
-            if (o->upd_kind == 5 && bq >= 8) {
-                /* contiguous spans: block b owns sub-tiles [b*S, (b+1)*S) of
-                 * 256*bq rows.  The block budget only sets the span length,
-                 * so locality never depends on a grid cap.  By default the
-                 * budget is the number of blocks the device holds at once:
-                 * a launch that fits keeps one sub-tile per block, a larger
-                 * one grows the span until the grid is a single resident
-                 * wave (measured best at the bench's 3.5M-row launches:
-                 * S=2, profiles/tile_update_note.md).  PBLOCKS or a forced
-                 * block count replace the budget, TILE_S the span itself. */
-                auto kern = k_update_tile<8, TILE_SLOTS, TILE_PROBES>;
-                if (bq == 16)
-                    kern = k_update_tile<16, TILE_SLOTS, TILE_PROBES>;
-                else if (bq == 12)
-                    kern = k_update_tile<12, TILE_SLOTS, TILE_PROBES>;
-                if (o->tile_resident_q != bq) {
-                    int per_cu = 0, cus = 0;
-                    hipError_t e1 = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                        &per_cu, kern, 256, 0);
-                    hipError_t e2 = hipDeviceGetAttribute(
-                        &cus, hipDeviceAttributeMultiprocessorCount,
-                        o->cfg.device);
-                    HIP_CHECK(o, e1);
-                    HIP_CHECK(o, e2);
-                    o->tile_resident = per_cu * cus > 0 ? per_cu * cus : 1;
-                    o->tile_resident_q = bq;
-                }
-                int64_t tiles = (n_rows / bq + 255) / 256;
-                if (tiles < 1) tiles = 1;
-                int64_t budget = o->tile_resident;
-                if (getenv("ARROYO_AMD_PBLOCKS")) budget = pcap;
-                if (o->force_blocks > 0) budget = o->force_blocks;
-                if (budget < 1) budget = 1;
-                int64_t span = (tiles + budget - 1) / budget;
-                if (const char *ev4 = getenv("ARROYO_AMD_TILE_S"))
-                    if (atoi(ev4) > 0) span = atoi(ev4);
-                int tblocks = (int)((tiles + span - 1) / span);
-                hipLaunchKernelGGL(kern, dim3(tblocks), dim3(256), 0,
-                                   o->stream, A, (int)span);
-            } else if (bq >= 16)
-                hipLaunchKernelGGL(k_update_batch_n<16>, dim3(pblocks),
-                                   dim3(256), 0, o->stream, A);
-            else if (bq >= 12)
-                hipLaunchKernelGGL(k_update_batch_n<12>, dim3(pblocks),
-                                   dim3(256), 0, o->stream, A);
-            else if (bq >= 8)
-                hipLaunchKernelGGL(k_update_batch_n<8>, dim3(pblocks),
-                                   dim3(256), 0, o->stream, A);
-            else if (bq >= 4)
-                hipLaunchKernelGGL(k_update_batch<4>, dim3(pblocks),
-                                   dim3(256), 0, o->stream, A);
-            else if (bq >= 2)
-                hipLaunchKernelGGL(k_update_batch<2>, dim3(pblocks),
-                                   dim3(256), 0, o->stream, A);
-            else
-                hipLaunchKernelGGL(k_update_batch_scalar, dim3(pblocks),
-                                   dim3(256), 0, o->stream, A);
-            int64_t tail = bq > 1 ? A.n_rows % bq : 0;
-            if (tail) {
-                /* quad/pair kernels skip the last n_rows % bq rows; finish
-                 * them with a tiny scalar launch (same parity) */
-                UpdateArgs T = A;
-                T.key_col = A.key_col + (A.n_rows - tail);
-                T.ts_col = A.ts_col + (A.n_rows - tail);
-                T.n_rows = tail;
-                hipLaunchKernelGGL(k_update_batch_scalar, dim3(1), dim3(64),
-                                   0, o->stream, T);
-            }
-        } else if (o->upd_kind == 1) {
-            if (pvec)
-                hipLaunchKernelGGL((k_update_packed<true, true>),
-                                   dim3(pblocks), dim3(256), 0, o->stream, A);
-            else
-                hipLaunchKernelGGL((k_update_packed<false, true>),
-                                   dim3(pblocks), dim3(256), 0, o->stream, A);
-        } else {
-            if (pvec)
-                hipLaunchKernelGGL((k_update_packed<true, false>),
-                                   dim3(pblocks), dim3(256), 0, o->stream, A);
-            else
-                hipLaunchKernelGGL((k_update_packed<false, false>),
-                                   dim3(pblocks), dim3(256), 0, o->stream, A);
-        }
-        if (sample) {
-            hipEventRecord(o->ev_pool[ev].second, o->stream);
-            o->ev_inflight.push_back(ev);
-        }
-        HIP_CHECK(o, hipGetLastError());
-        o->update_rows += n_rows;
-        o->launches++;
-        return 0;
-    }
-    int slots = 1024;
-    if (const char *e = getenv("ARROYO_AMD_LDS_SLOTS")) slots = atoi(e);
-    bool radix = o->use_radix && o->cfg.n_keys == 1 &&
-                 o->cfg.n_value_cols == 0 && o->agg.n_aggs == 1 &&
-                 o->agg.op[0] == AMD_AGG_COUNT && n_rows >= (1 << 18);
-    if (radix) {
-        if (launch_update_radix(o, dcols[0], dcols[1], n_rows, ts_offset))
-            return 1;
-        if (sample) {
-            hipEventRecord(o->ev_pool[ev].second, o->stream);
-            o->ev_inflight.push_back(ev);
-        }
-        o->update_rows += n_rows;
-        o->launches++;
-        return 0;
-    }
-    size_t shmem = (size_t)slots * o->agg.n_aggs * 16;
-    bool count_only = o->agg.n_aggs == 1 && o->agg.op[0] == AMD_AGG_COUNT &&
-                      o->kmode == 0;
-    if (vec) {
-        bool cmb = count_only && o->use_wavecmb;
-        if (slots >= 2048)
-            hipLaunchKernelGGL((cmb ? k_update_lds_vec<2048, true, true>
-                                : count_only
-                                    ? k_update_lds_vec<2048, true>
-                                    : k_update_lds_vec<2048, false>),
-                               dim3(blocks), dim3(256), shmem, o->stream, A);
-        else
-            hipLaunchKernelGGL((cmb ? k_update_lds_vec<1024, true, true>
-                                : count_only
-                                    ? k_update_lds_vec<1024, true>
-                                    : k_update_lds_vec<1024, false>),
-                               dim3(blocks), dim3(256), shmem, o->stream, A);
-    } else if (o->use_lds) {
-        shmem = (size_t)LDS_SLOTS * o->agg.n_aggs * 16;
-        hipLaunchKernelGGL(k_update_lds, dim3(blocks), dim3(256), shmem,
-                           o->stream, A);
-    } else {
-        hipLaunchKernelGGL(k_update, dim3(blocks), dim3(256), 0, o->stream, A);
+    switch (o->upd_kind) {
+    case UPD_LDS: launch_lds(o, A); break;
+    case UPD_BATCH: launch_batch(o, A); break;
+    case UPD_TILE:
+        if (launch_tile(o, A)) return 1;
+        break;
     }
     if (sample) {
         hipEventRecord(o->ev_pool[ev].second, o->stream);
@@ -3953,16 +2976,7 @@ static int fire_window(GpuOp *o, const std::vector<uint32_t> &src,
                 slots = 2048;   /* 4096 two-word states blow the LDS */
             size_t shmem = (size_t)slots *
                            ((M.use_cpi && o->cpi_ew == 2) ? 8 : na * 16);
-            if (o->ring.packed) {
-                if (mfs >= 2048)
-                    hipLaunchKernelGGL((k_merge_fused<2048, true>),
-                                       dim3(o->ring.C / range), dim3(256),
-                                       shmem, fs, M);
-                else
-                    hipLaunchKernelGGL((k_merge_fused<1024, true>),
-                                       dim3(o->ring.C / range), dim3(256),
-                                       shmem, fs, M);
-            } else if (slots == 4096)
+            if (slots == 4096)
                 hipLaunchKernelGGL(k_merge_fused<4096>,
                                    dim3(o->ring.C / range), dim3(256),
                                    shmem, fs, M);
@@ -4176,8 +3190,8 @@ static int dual_ok(GpuOp *o) {
      * Read per call (not latched) so tests can exercise the path. */
     const char *ev = getenv("ARROYO_AMD_DUAL");
     int on = ev ? atoi(ev) != 0 : 0;
-    return on && o->cpi_entries && o->cpi_ew == 2 && !o->ring.packed &&
-           !o->mk && o->agg.n_aggs == 1 && o->agg.op[0] == AMD_AGG_COUNT &&
+    return on && o->cpi_entries && o->cpi_ew == 2 && !o->mk &&
+           o->agg.n_aggs == 1 && o->agg.op[0] == AMD_AGG_COUNT &&
            !o->agg.isf[0];
 }
 
@@ -4712,7 +3726,6 @@ API void arroyo_amd_destroy(void *h) {
     }
     hipFree(o->ring.keys);
     hipFree(o->ring.state);
-    hipFree(o->ring.slots);
     hipFree(o->d_status);
     hipHostFree(o->h_status);
     hipFree(o->ring.spec_used);
@@ -4723,10 +3736,6 @@ API void arroyo_amd_destroy(void *h) {
     hipFree(o->d_emitted);
     hipFree(o->d_fire_cur);
     hipFree(o->d_fire_cur2);
-    hipFree(o->rdx_key);
-    hipFree(o->rdx_ts);
-    hipFree(o->rdx_hist);
-    hipFree(o->rdx_tmp);
     hipFree(o->cpi_entries);
     hipFree(o->cpi_cnt);
     hipFree(o->d_dict_digest);
@@ -4734,10 +3743,6 @@ API void arroyo_amd_destroy(void *h) {
     hipFree(o->d_dict_ready);
     hipFree(o->d_keyid_in);
     hipFree(o->d_keyid_out);
-    hipFree(o->rdx2_skey);
-    hipFree(o->rdx2_spane);
-    hipFree(o->rdx2_hist);
-    hipFree(o->rdx2_tmp);
     for (int i = 0; i < o->stg.ncols; i++) {
         hipHostFree(o->stg.buf[i]);
         hipFree(o->stg.dbuf[i]);
@@ -4890,773 +3895,4 @@ API int arroyo_amd_partition(const int64_t *d_keys, const int64_t *d_vals,
     hipFree(d_pid);
     hipFree(d_counts);
     return e == hipSuccess ? 0 : 1;
-}
-
-/* ================================================================== */
-/* Instant (windowed stream-stream) join: MI355X-native equivalent of
- * InstantJoin (crates/arroyo-worker/src/arrow/instant_join.rs) behind the
- * arroyo_amd_join_* C ABI (include/arroyo_amd.h).
- *
- * Design (not a translation): instead of per-instant DataFusion exec
- * streams fed through channels (instant_join.rs:86-107), both sides'
- * rows land directly in a device-resident instant table: `instants` slots,
- * each an append buffer per side (key + value columns, SoA).  A fused
- * append kernel (K2-equivalent routing + buffering) claims the instant
- * slot by CAS on its tag and appends with a wave-aggregated cursor.  On
- * watermark the host fires instants < wm in timestamp order
- * (instant_join.rs:265-281): per instant, a build kernel chains the left
- * rows into a hash multimap (LDS-free; the map is small and L2-resident)
- * and a probe kernel streams the right rows and emits matches (K6) --
- * or, for n_keys == 0 (join on the window itself), a cross-product
- * kernel with no atomics at all. */
-
-#define JERR_LATE      4
-#define JERR_INSTANTS  5
-#define JERR_ROWS_CAP  6
-#define JERR_OUT_CAP   7
-
-struct JAppendArgs {
-    const int64_t *cols[6];   /* key?, vals..., ts */
-    int32_t n_keys, n_vals;
-    int64_t n_rows;
-    uint64_t *tag;            /* [I] */
-    unsigned long long *cursor; /* [I] */
-    int64_t *key;             /* [I*cap] */
-    int64_t *vals;            /* [n_vals][I*cap] */
-    uint32_t I, cap;
-    int has_wm; uint64_t wm;
-    int *err;
-};
-
-/* claim-or-find the slot for instant t (open addressing over the tags) */
-__device__ inline int32_t claim_instant(uint64_t *tag, uint32_t I, uint64_t t,
-                                        int *err) {
-    uint32_t m = I - 1;
-    uint32_t j = (uint32_t)hash64(t) & m;
-    for (uint32_t probes = 0; probes < I; probes++) {
-        uint64_t cur = tag[j];
-        if (cur == t) return (int32_t)j;
-        if (cur == EMPTY_TAG) {
-            uint64_t old = atomicCAS((unsigned long long *)&tag[j],
-                                     (unsigned long long)EMPTY_TAG,
-                                     (unsigned long long)t);
-            if (old == EMPTY_TAG || old == t) return (int32_t)j;
-        }
-        j = (j + 1) & m;
-    }
-    *err = JERR_INSTANTS;
-    return -1;
-}
-
-__global__ void __launch_bounds__(256)
-k_join_append(JAppendArgs A) {
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const int64_t *ts = A.cols[A.n_keys + A.n_vals];
-    int lane = (int)(threadIdx.x & 63);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-         i < A.n_rows; i += stride) {
-        uint64_t t = (uint64_t)ts[i];
-        if (A.has_wm && t < A.wm) { *A.err = JERR_LATE; continue; }
-        /* wave-uniform fast path: one leader claims slot + cursor range */
-        unsigned long long act = __ballot(1);
-        int leader = (int)(__ffsll((long long)act) - 1);
-        uint64_t t0 = (uint64_t)__shfl((long long)t, leader, 64);
-        int32_t slot;
-        uint64_t idx;
-        if (__all(t == t0)) {
-            int cnt = __popcll((long long)act);
-            int rank = __popcll((long long)(act & ((1ULL << lane) - 1)));
-            unsigned long long base = 0;
-            int32_t s0 = -1;
-            if (lane == leader) {
-                s0 = claim_instant(A.tag, A.I, t, A.err);
-                if (s0 >= 0)
-                    base = atomicAdd(&A.cursor[s0], (unsigned long long)cnt);
-            }
-            slot = (int32_t)__shfl((int)s0, leader, 64);
-            base = (unsigned long long)__shfl((long long)base, leader, 64);
-            if (slot < 0) continue;
-            idx = base + (uint64_t)rank;
-        } else {
-            slot = claim_instant(A.tag, A.I, t, A.err);
-            if (slot < 0) continue;
-            idx = atomicAdd(&A.cursor[slot], 1ULL);
-        }
-        if (idx >= A.cap) { *A.err = JERR_ROWS_CAP; continue; }
-        size_t off = (size_t)slot * A.cap + idx;
-        int c = 0;
-        if (A.n_keys) A.key[off] = A.cols[c++][i];
-        for (int v = 0; v < A.n_vals; v++)
-            A.vals[(size_t)v * A.I * A.cap + off] = A.cols[c++][i];
-    }
-}
-
-/* build a chained hash multimap over one instant's left rows.  `base` is
- * the slot's global row offset (slot*cap): chain links are global indices so
- * several slots holding the same instant (possible after slot recycling — a
- * retired slot's tag hole lets a later append re-claim an earlier probe
- * position) can be built into ONE map and joined as one logical instant. */
-struct JBuildArgs {
-    const int64_t *key;   /* left keys of this slot, [nl] */
-    int64_t nl;
-    int64_t base;         /* slot*cap: global index of this slot's row 0 */
-    int64_t *b_keys;      /* [H] open-addressing key table */
-    int32_t *b_head;      /* [H] chain heads (-1 empty) */
-    int32_t *b_next;      /* [I*cap], indexed by global row index */
-    uint32_t H;
-    int *err;
-};
-
-__global__ void __launch_bounds__(256)
-k_join_build(JBuildArgs B) {
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-         i < B.nl; i += stride) {
-        int64_t key = B.key[i];
-        int64_t s = table_upsert(B.b_keys, B.H, key, B.err);
-        if (s < 0) continue;
-        B.b_next[B.base + i] =
-            atomicExch(&B.b_head[s], (int32_t)(B.base + i));
-    }
-}
-
-struct JProbeArgs {
-    const int64_t *r_key;     /* right keys of this slot, [nr] */
-    const int64_t *l_key;     /* left key plane base (global row index) */
-    const int64_t *l_vals;    /* [n_left_vals][I*cap] base of left side */
-    const int64_t *r_vals;    /* [n_right_vals][I*cap] base of right side */
-    size_t l_off, r_off;      /* slot*cap element offset */
-    size_t plane;             /* I*cap: stride between value planes */
-    int64_t nr;
-    const int64_t *b_keys;
-    const int32_t *b_head;
-    const int32_t *b_next;
-    uint32_t H;
-    int32_t n_keys, nlv, nrv;
-    int32_t jt;               /* AMD_JOIN_* */
-    uint32_t *l_hit;          /* [plane/32] matched-left bitmap (outer) */
-    uint64_t instant;
-    int64_t *out[16];
-    unsigned long long *n_out;
-    int64_t out_cap;
-    int *err;
-};
-
-/* li/ri == -1: that side absent (outer join) -> zero-filled values,
- * presence flag 0.  li is a GLOBAL row index when the chain map is in
- * play (l_off = 0), slot-relative otherwise. */
-__device__ inline void jemit_row(const JProbeArgs &P, int64_t key, int64_t li,
-                                 int64_t ri, int64_t r) {
-    if (r >= P.out_cap) { *P.err = JERR_OUT_CAP; return; }
-    int col = 0;
-    if (P.n_keys) P.out[col++][r] = key;
-    for (int v = 0; v < P.nlv; v++)
-        P.out[col++][r] =
-            li >= 0 ? P.l_vals[(size_t)v * P.plane + P.l_off + li] : 0;
-    for (int v = 0; v < P.nrv; v++)
-        P.out[col++][r] =
-            ri >= 0 ? P.r_vals[(size_t)v * P.plane + P.r_off + ri] : 0;
-    P.out[col++][r] = (int64_t)P.instant;
-    if (P.jt != AMD_JOIN_INNER) {
-        P.out[col++][r] = li >= 0;
-        P.out[col][r] = ri >= 0;
-    }
-}
-
-__global__ void __launch_bounds__(256)
-k_join_probe(JProbeArgs P) {
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    uint32_t m = P.H - 1;
-    const bool emit_r = P.jt == AMD_JOIN_RIGHT || P.jt == AMD_JOIN_FULL;
-    const bool track_l = P.l_hit != nullptr;
-    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-         j < P.nr; j += stride) {
-        int64_t key = P.r_key[j];
-        uint64_t s = hash64((uint64_t)key) & m;
-        int32_t head = -1;
-        for (uint32_t probes = 0; probes < P.H; probes++) {
-            int64_t k = P.b_keys[s];
-            if (k == key) { head = P.b_head[s]; break; }
-            if (k == EMPTY_KEY) break;
-            s = (s + 1) & m;
-        }
-        bool hit = false;
-        for (int32_t li = head; li >= 0; li = P.b_next[li]) {
-            int64_t r = (int64_t)atomicAdd(P.n_out, 1ULL);
-            jemit_row(P, key, li, j, r);
-            hit = true;
-            if (track_l)
-                atomicOr(&P.l_hit[(uint32_t)li >> 5], 1u << ((uint32_t)li & 31u));
-        }
-        if (!hit && emit_r) {
-            int64_t r = (int64_t)atomicAdd(P.n_out, 1ULL);
-            jemit_row(P, key, -1, j, r);
-        }
-    }
-}
-
-/* pad-every-right-row kernel: window-condition (n_keys == 0) outer joins
- * with an empty left side have no key plane to probe, so emit the right
- * rows directly (slot-relative ri against P.r_off) */
-__global__ void __launch_bounds__(256)
-k_join_pad_right(JProbeArgs P) {
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t ri = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-         ri < P.nr; ri += stride) {
-        int64_t r = (int64_t)atomicAdd(P.n_out, 1ULL);
-        jemit_row(P, 0, -1, ri, r);
-    }
-}
-
-/* outer-join left pass: emit every left row of one slot whose matched bit
- * is unset ([base, base+nl) global row indices); with a zeroed bitmap this
- * doubles as the pad-every-left-row kernel for empty-right instants */
-__global__ void __launch_bounds__(256)
-k_join_unmatched_left(JProbeArgs P, int64_t base, int64_t nl) {
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-         i < nl; i += stride) {
-        int64_t li = base + i;
-        if (P.l_hit[(uint32_t)li >> 5] & (1u << ((uint32_t)li & 31u)))
-            continue;
-        int64_t r = (int64_t)atomicAdd(P.n_out, 1ULL);
-        jemit_row(P, P.n_keys ? P.l_key[li] : 0, li, -1, r);
-    }
-}
-
-/* n_keys == 0: cross product of the instant's sides, no atomics;
- * `out_base` offsets the output rows so one logical instant spread across
- * several (left slot, right slot) pairs writes disjoint output ranges */
-__global__ void __launch_bounds__(256)
-k_join_cross(JProbeArgs P, int64_t nl, int64_t out_base) {
-    int64_t total = nl * P.nr;
-    int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-         i < total; i += stride)
-        jemit_row(P, 0, i / P.nr, i % P.nr, out_base + i);
-}
-
-struct GpuJoin {
-    AmdJoinConfig cfg;
-    uint32_t I, cap, H;
-    int64_t out_cap;
-    uint64_t *tag;
-    unsigned long long *cursor[2];
-    int64_t *key[2];
-    int64_t *vals[2];          /* [n_vals][I*cap] */
-    int64_t *b_keys; int32_t *b_head; int32_t *b_next;
-    uint32_t *l_hit;           /* [I*cap/32] matched-left bitmap (outer) */
-    int64_t *d_out[16];
-    unsigned long long *d_n_out;
-    int *d_err;
-    int64_t *stg[2][8];        /* pinned host + device staging per side */
-    int64_t *stg_d[2][8];
-    int64_t stg_cap;
-    std::vector<std::vector<int64_t>> host_out;
-    int out_cols;
-    int has_wm; uint64_t wm;
-    int64_t emitted_device_rows;
-    hipStream_t stream;
-    char err_msg[512];
-};
-
-#define JHIP(o, call)                                                         \
-    do {                                                                      \
-        hipError_t _e = (call);                                               \
-        if (_e != hipSuccess) {                                               \
-            snprintf((o)->err_msg, sizeof (o)->err_msg, "%s:%d hip: %s",      \
-                     __FILE__, __LINE__, hipGetErrorString(_e));              \
-            return 1;                                                         \
-        }                                                                     \
-    } while (0)
-
-API void *arroyo_amd_join_create(const AmdJoinConfig *cfg) {
-    if (!cfg || cfg->n_keys < 0 || cfg->n_keys > 1 || cfg->n_left_vals < 0 ||
-        cfg->n_right_vals < 0 || cfg->n_left_vals > 4 ||
-        cfg->n_right_vals > 4 || cfg->join_type < 0 ||
-        cfg->join_type > AMD_JOIN_FULL) {
-        snprintf(g_err, sizeof g_err, "invalid join config");
-        return nullptr;
-    }
-    GpuJoin *o = new GpuJoin();
-    o->cfg = *cfg;
-    o->I = cfg->instants ? cfg->instants : 128;
-    o->cap = 1u << (cfg->log2_rows_cap ? cfg->log2_rows_cap : 15);
-    o->H = o->cap * 2;
-    o->out_cap = 1ll << (cfg->log2_out_cap ? cfg->log2_out_cap : 20);
-    o->out_cols = cfg->n_keys + cfg->n_left_vals + cfg->n_right_vals + 1 +
-                  (cfg->join_type != AMD_JOIN_INNER ? 2 : 0);
-    if (hipSetDevice(cfg->device) != hipSuccess) {
-        snprintf(g_err, sizeof g_err,
-                 "hipSetDevice(%d) failed: no HIP device (no CPU fallback)",
-                 cfg->device);
-        delete o;
-        return nullptr;
-    }
-    hipError_t e;
-    auto fail = [&](const char *what, hipError_t e2) {
-        snprintf(g_err, sizeof g_err, "%s: %s", what, hipGetErrorString(e2));
-        delete o;
-        return nullptr;
-    };
-#define JALLOC(p, bytes)                                                      \
-    if ((e = hipMalloc((void **)&(p), (bytes))) != hipSuccess)                \
-        return fail(#p, e);
-    size_t plane = (size_t)o->I * o->cap;
-    JALLOC(o->tag, (size_t)o->I * 8);
-    for (int s = 0; s < 2; s++) {
-        int nv = s == 0 ? cfg->n_left_vals : cfg->n_right_vals;
-        JALLOC(o->cursor[s], (size_t)o->I * 8);
-        if (cfg->n_keys) JALLOC(o->key[s], plane * 8);
-        if (nv) JALLOC(o->vals[s], (size_t)nv * plane * 8);
-    }
-    JALLOC(o->b_keys, (size_t)o->H * 8);
-    JALLOC(o->b_head, (size_t)o->H * 4);
-    JALLOC(o->b_next, (size_t)o->I * o->cap * 4);
-    if (cfg->join_type == AMD_JOIN_LEFT || cfg->join_type == AMD_JOIN_FULL)
-        JALLOC(o->l_hit, plane / 32 * 4 + 4);
-    for (int i = 0; i < o->out_cols && i < 16; i++)
-        JALLOC(o->d_out[i], (size_t)o->out_cap * 8);
-    JALLOC(o->d_n_out, 8);
-    JALLOC(o->d_err, 4);
-#undef JALLOC
-    hipMemset(o->tag, 0xFF, (size_t)o->I * 8);
-    for (int s = 0; s < 2; s++)
-        hipMemset(o->cursor[s], 0, (size_t)o->I * 8);
-    hipMemset(o->d_err, 0, 4);
-    hipStreamCreate(&o->stream);
-    o->stg_cap = 1 << 20;
-    for (int s = 0; s < 2; s++) {
-        int nc = cfg->n_keys + (s == 0 ? cfg->n_left_vals : cfg->n_right_vals) + 1;
-        for (int c = 0; c < nc; c++) {
-            if (hipHostMalloc((void **)&o->stg[s][c], (size_t)o->stg_cap * 8) !=
-                    hipSuccess ||
-                hipMalloc((void **)&o->stg_d[s][c], (size_t)o->stg_cap * 8) !=
-                    hipSuccess) {
-                snprintf(g_err, sizeof g_err, "join staging alloc failed");
-                delete o;
-                return nullptr;
-            }
-        }
-    }
-    o->host_out.resize(o->out_cols);
-    return o;
-}
-
-API const char *arroyo_amd_join_last_error(void *h) {
-    return h ? ((GpuJoin *)h)->err_msg : g_err;
-}
-
-static int join_check_err(GpuJoin *o) {
-    int e = 0;
-    JHIP(o, hipMemcpyAsync(&e, o->d_err, 4, hipMemcpyDeviceToHost, o->stream));
-    JHIP(o, hipStreamSynchronize(o->stream));
-    if (!e) return 0;
-    const char *msg = e == JERR_LATE      ? "batch timestamp before watermark"
-                      : e == JERR_INSTANTS ? "live-instant table full; raise instants"
-                      : e == JERR_ROWS_CAP ? "per-instant row buffer full; raise log2_rows_cap"
-                      : e == JERR_OUT_CAP  ? "output buffer full; raise log2_out_cap"
-                      : e == ERR_TABLE_FULL ? "join build table full"
-                                            : "device error";
-    snprintf(o->err_msg, sizeof o->err_msg, "%s", msg);
-    return 1;
-}
-
-static int join_append_device(GpuJoin *o, int side, const int64_t *const *dcols,
-                              int64_t n_rows) {
-    if (n_rows == 0) return 0;
-    JAppendArgs A = {};
-    int nv = side == 0 ? o->cfg.n_left_vals : o->cfg.n_right_vals;
-    for (int c = 0; c < o->cfg.n_keys + nv + 1; c++) A.cols[c] = dcols[c];
-    A.n_keys = o->cfg.n_keys;
-    A.n_vals = nv;
-    A.n_rows = n_rows;
-    A.tag = o->tag;
-    A.cursor = o->cursor[side];
-    A.key = o->key[side];
-    A.vals = o->vals[side];
-    A.I = o->I;
-    A.cap = o->cap;
-    A.has_wm = o->has_wm;
-    A.wm = o->wm;
-    A.err = o->d_err;
-    int64_t want = (n_rows + 255) / 256;
-    int blocks = (int)(want > 1024 ? 1024 : (want < 1 ? 1 : want));
-    hipLaunchKernelGGL(k_join_append, dim3(blocks), dim3(256), 0, o->stream, A);
-    JHIP(o, hipGetLastError());
-    return 0;
-}
-
-API int arroyo_amd_join_process_batch(void *h, int32_t side,
-                                      const int64_t *const *cols,
-                                      int32_t n_cols, int64_t n_rows) {
-    GpuJoin *o = (GpuJoin *)h;
-    int nv = side == 0 ? o->cfg.n_left_vals : o->cfg.n_right_vals;
-    if (n_cols != o->cfg.n_keys + nv + 1) {
-        snprintf(o->err_msg, sizeof o->err_msg, "side %d expects %d cols",
-                 side, o->cfg.n_keys + nv + 1);
-        return 1;
-    }
-    int64_t done = 0;
-    while (done < n_rows) {
-        int64_t take = n_rows - done;
-        if (take > o->stg_cap) take = o->stg_cap;
-        const int64_t *dcols[6];
-        for (int c = 0; c < n_cols; c++) {
-            memcpy(o->stg[side][c], cols[c] + done, (size_t)take * 8);
-            JHIP(o, hipMemcpyAsync(o->stg_d[side][c], o->stg[side][c],
-                                   (size_t)take * 8, hipMemcpyHostToDevice,
-                                   o->stream));
-            dcols[c] = o->stg_d[side][c];
-        }
-        if (join_append_device(o, side, dcols, take)) return 1;
-        /* staging reused next iteration: wait for this append to finish */
-        JHIP(o, hipStreamSynchronize(o->stream));
-        done += take;
-    }
-    return 0;
-}
-
-API int arroyo_amd_join_process_batch_device(void *h, int32_t side,
-                                             const int64_t *const *dcols,
-                                             int32_t n_cols, int64_t n_rows) {
-    GpuJoin *o = (GpuJoin *)h;
-    int nv = side == 0 ? o->cfg.n_left_vals : o->cfg.n_right_vals;
-    if (n_cols != o->cfg.n_keys + nv + 1) {
-        snprintf(o->err_msg, sizeof o->err_msg, "side %d expects %d cols",
-                 side, o->cfg.n_keys + nv + 1);
-        return 1;
-    }
-    return join_append_device(o, side, dcols, n_rows);
-}
-
-/* Fire one logical instant.  `slots` is every table slot holding this
- * instant's rows — normally one, but slot recycling can split an instant
- * across slots (see k_join_build comment); the group joins as a whole so no
- * cross-slot match is lost. */
-static int join_fire(GpuJoin *o, uint64_t instant,
-                     const std::vector<uint32_t> &slots,
-                     const std::vector<unsigned long long> &c0,
-                     const std::vector<unsigned long long> &c1) {
-    size_t plane = (size_t)o->I * o->cap;
-    JHIP(o, hipMemsetAsync(o->d_n_out, 0, 8, o->stream));
-    JProbeArgs P = {};
-    P.l_vals = o->vals[0];
-    P.r_vals = o->vals[1];
-    P.plane = plane;
-    P.b_keys = o->b_keys;
-    P.b_head = o->b_head;
-    P.b_next = o->b_next;
-    P.H = o->H;
-    P.n_keys = o->cfg.n_keys;
-    P.nlv = o->cfg.n_left_vals;
-    P.nrv = o->cfg.n_right_vals;
-    P.jt = o->cfg.join_type;
-    P.l_key = o->key[0];
-    P.instant = instant;
-    for (int i = 0; i < o->out_cols && i < 16; i++) P.out[i] = o->d_out[i];
-    P.n_out = o->d_n_out;
-    P.out_cap = o->out_cap;
-    P.err = o->d_err;
-    const bool emit_l =
-        P.jt == AMD_JOIN_LEFT || P.jt == AMD_JOIN_FULL;
-    const bool emit_r =
-        P.jt == AMD_JOIN_RIGHT || P.jt == AMD_JOIN_FULL;
-    unsigned long long nl = 0, nr = 0;
-    for (uint32_t s : slots) { nl += c0[s]; nr += c1[s]; }
-    unsigned long long n = 0;
-    auto pad_left_slots = [&](bool use_bitmap) -> int {
-        /* emit left rows whose matched bit is unset; with use_bitmap false
-         * the bitmap is zeroed first so every row emits (empty right) */
-        for (uint32_t ls : slots) {
-            if (!c0[ls]) continue;
-            int64_t base = (int64_t)ls * o->cap;
-            if (!use_bitmap)
-                JHIP(o, hipMemsetAsync(o->l_hit + base / 32, 0,
-                                       (size_t)o->cap / 32 * 4, o->stream));
-            JProbeArgs Q = P;
-            Q.l_off = 0;
-            Q.l_hit = o->l_hit;
-            int64_t want = ((int64_t)c0[ls] + 255) / 256;
-            int blocks = (int)(want > 1024 ? 1024 : (want < 1 ? 1 : want));
-            hipLaunchKernelGGL(k_join_unmatched_left, dim3(blocks), dim3(256),
-                               0, o->stream, Q, base, (int64_t)c0[ls]);
-            JHIP(o, hipGetLastError());
-        }
-        return 0;
-    };
-    if (o->cfg.n_keys == 0) {
-        if (nl && nr) {
-            int64_t total = (int64_t)nl * (int64_t)nr;
-            if (total > o->out_cap) {
-                snprintf(o->err_msg, sizeof o->err_msg,
-                         "output buffer full; raise log2_out_cap");
-                return 1;
-            }
-            int64_t base = 0;
-            for (uint32_t ls : slots) {
-                if (!c0[ls]) continue;
-                for (uint32_t rs : slots) {
-                    if (!c1[rs]) continue;
-                    int64_t pair = (int64_t)c0[ls] * (int64_t)c1[rs];
-                    P.l_off = (size_t)ls * o->cap;
-                    P.r_off = (size_t)rs * o->cap;
-                    P.nr = (int64_t)c1[rs];
-                    int64_t want = (pair + 255) / 256;
-                    int blocks =
-                        (int)(want > 1024 ? 1024 : (want < 1 ? 1 : want));
-                    hipLaunchKernelGGL(k_join_cross, dim3(blocks), dim3(256),
-                                       0, o->stream, P, (int64_t)c0[ls], base);
-                    JHIP(o, hipGetLastError());
-                    base += pair;
-                }
-            }
-            n = (unsigned long long)total;
-        } else if (nl && emit_l) {
-            if (pad_left_slots(false)) return 1;
-            JHIP(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
-                                   o->stream));
-        } else if (nr && emit_r) {
-            /* no key plane exists when n_keys == 0: pad the right rows
-             * directly instead of probing */
-            for (uint32_t rs : slots) {
-                if (!c1[rs]) continue;
-                P.r_off = (size_t)rs * o->cap;
-                P.nr = (int64_t)c1[rs];
-                int64_t want = (P.nr + 255) / 256;
-                int blocks = (int)(want > 1024 ? 1024 : want);
-                hipLaunchKernelGGL(k_join_pad_right, dim3(blocks), dim3(256),
-                                   0, o->stream, P);
-                JHIP(o, hipGetLastError());
-            }
-            JHIP(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
-                                   o->stream));
-        }
-    } else if ((nl && nr) || (nl && emit_l) || (nr && emit_r)) {
-        bool probes = nr && (nl || emit_r);
-        if (probes || nl) {
-            JHIP(o, hipMemsetAsync(o->b_keys, 0xFF, (size_t)o->H * 8,
-                                   o->stream));
-            JHIP(o, hipMemsetAsync(o->b_head, 0xFF, (size_t)o->H * 4,
-                                   o->stream));
-        }
-        for (uint32_t ls : slots) {
-            if (!c0[ls]) continue;
-            JBuildArgs B = {};
-            B.key = o->key[0] + (size_t)ls * o->cap;
-            B.nl = (int64_t)c0[ls];
-            B.base = (int64_t)ls * o->cap;
-            B.b_keys = o->b_keys;
-            B.b_head = o->b_head;
-            B.b_next = o->b_next;
-            B.H = o->H;
-            B.err = o->d_err;
-            int64_t want = (B.nl + 255) / 256;
-            int blocks = (int)(want > 1024 ? 1024 : want);
-            hipLaunchKernelGGL(k_join_build, dim3(blocks), dim3(256), 0,
-                               o->stream, B);
-            JHIP(o, hipGetLastError());
-        }
-        if (emit_l)
-            for (uint32_t ls : slots) {
-                if (!c0[ls]) continue;
-                JHIP(o, hipMemsetAsync(
-                            o->l_hit + (size_t)ls * o->cap / 32, 0,
-                            (size_t)o->cap / 32 * 4, o->stream));
-            }
-        /* chain links are global row indices: probe reads left values at
-         * l_vals[v*plane + li] directly, so l_off = 0 */
-        P.l_off = 0;
-        P.l_hit = emit_l ? o->l_hit : nullptr;
-        if (probes)
-            for (uint32_t rs : slots) {
-                if (!c1[rs]) continue;
-                P.r_key = o->key[1] + (size_t)rs * o->cap;
-                P.r_off = (size_t)rs * o->cap;
-                P.nr = (int64_t)c1[rs];
-                int64_t want = (P.nr + 255) / 256;
-                int blocks = (int)(want > 1024 ? 1024 : want);
-                hipLaunchKernelGGL(k_join_probe, dim3(blocks), dim3(256), 0,
-                                   o->stream, P);
-                JHIP(o, hipGetLastError());
-            }
-        if (emit_l && nl && pad_left_slots(true)) return 1;
-        JHIP(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
-                               o->stream));
-    }
-    /* retire every slot of the instant */
-    for (uint32_t s : slots) {
-        JHIP(o, hipMemsetAsync(o->tag + s, 0xFF, 8, o->stream));
-        JHIP(o, hipMemsetAsync(o->cursor[0] + s, 0, 8, o->stream));
-        JHIP(o, hipMemsetAsync(o->cursor[1] + s, 0, 8, o->stream));
-    }
-    JHIP(o, hipStreamSynchronize(o->stream));
-    if (n == 0) return 0;
-    if ((int64_t)n > o->out_cap) {
-        snprintf(o->err_msg, sizeof o->err_msg,
-                 "output buffer full; raise log2_out_cap");
-        return 1;
-    }
-    if (o->cfg.emit_to_host) {
-        for (int i = 0; i < o->out_cols; i++) {
-            size_t old = o->host_out[i].size();
-            o->host_out[i].resize(old + n);
-            JHIP(o, hipMemcpyAsync(o->host_out[i].data() + old, o->d_out[i],
-                                   (size_t)n * 8, hipMemcpyDeviceToHost,
-                                   o->stream));
-        }
-        JHIP(o, hipStreamSynchronize(o->stream));
-    } else {
-        o->emitted_device_rows += (int64_t)n;
-    }
-    return 0;
-}
-
-
-/* Arrow validity bitmaps for null-padded value columns (LSB bit order,
- * see AmdOutBatch doc): left vals valid where the left-presence column is
- * set, right vals likewise.  The presence columns stay in the output. */
-static void fill_join_validity(AmdOutBatch *out, int base_l, int nlv,
-                               int nrv, int lp_col, int rp_col) {
-    int64_t n = out->n_rows;
-    out->validity = (uint8_t **)calloc(out->n_cols, sizeof(uint8_t *));
-    if (!out->validity || n == 0) return;
-    size_t nbytes = (size_t)((n + 7) / 8);
-    for (int g = 0; g < 2; g++) {
-        int base = g == 0 ? base_l : base_l + nlv;
-        int cnt = g == 0 ? nlv : nrv;
-        const int64_t *pres =
-            (const int64_t *)out->cols[g == 0 ? lp_col : rp_col];
-        for (int c = base; c < base + cnt; c++) {
-            uint8_t *bm = (uint8_t *)calloc(nbytes, 1);
-            if (!bm) continue;
-            for (int64_t r = 0; r < n; r++)
-                if (pres[r]) bm[r >> 3] |= (uint8_t)(1u << (r & 7));
-            out->validity[c] = bm;
-        }
-    }
-}
-
-API int arroyo_amd_join_handle_watermark(void *h, uint64_t wm,
-                                         AmdOutBatch *out) {
-    GpuJoin *o = (GpuJoin *)h;
-    if (join_check_err(o)) return 1;
-    o->has_wm = 1;
-    o->wm = wm;
-    /* snapshot live instants + row counts */
-    std::vector<uint64_t> tags(o->I);
-    std::vector<unsigned long long> c0(o->I), c1(o->I);
-    JHIP(o, hipMemcpyAsync(tags.data(), o->tag, (size_t)o->I * 8,
-                           hipMemcpyDeviceToHost, o->stream));
-    JHIP(o, hipMemcpyAsync(c0.data(), o->cursor[0], (size_t)o->I * 8,
-                           hipMemcpyDeviceToHost, o->stream));
-    JHIP(o, hipMemcpyAsync(c1.data(), o->cursor[1], (size_t)o->I * 8,
-                           hipMemcpyDeviceToHost, o->stream));
-    JHIP(o, hipStreamSynchronize(o->stream));
-    /* timestamp order (instant_join.rs:265-281); an instant may occupy
-     * several slots after recycling — fire them as one group */
-    std::map<uint64_t, std::vector<uint32_t>> fired;
-    for (uint32_t s = 0; s < o->I; s++)
-        if (tags[s] != EMPTY_TAG && tags[s] < wm) fired[tags[s]].push_back(s);
-    for (auto &kv : fired)
-        if (join_fire(o, kv.first, kv.second, c0, c1))
-            return 1;
-    if (out) {
-        memset(out, 0, sizeof *out);
-        int64_t n = o->host_out.empty() ? 0 : (int64_t)o->host_out[0].size();
-        out->n_rows = n;
-        out->n_cols = o->out_cols;
-        out->cols = (void **)calloc(o->out_cols, sizeof(void *));
-        out->is_f64 = (int32_t *)calloc(o->out_cols, sizeof(int32_t));
-        for (int i = 0; i < o->out_cols; i++) {
-            out->cols[i] = malloc((size_t)(n ? n : 1) * 8);
-            if (n) memcpy(out->cols[i], o->host_out[i].data(), (size_t)n * 8);
-        }
-        if (o->cfg.join_type != AMD_JOIN_INNER) {
-            /* [key?, lvals, rvals, instant, lp, rp] */
-            int base_l = o->cfg.n_keys;
-            int inst = base_l + o->cfg.n_left_vals + o->cfg.n_right_vals;
-            fill_join_validity(out, base_l, o->cfg.n_left_vals,
-                               o->cfg.n_right_vals, inst + 1, inst + 2);
-        }
-        for (auto &v : o->host_out) v.clear();
-    }
-    return 0;
-}
-
-/* drain one side's buffered rows: [key?, vals..., _timestamp] */
-API int arroyo_amd_join_checkpoint_drain(void *h, int32_t side,
-                                         AmdOutBatch *out) {
-    GpuJoin *o = (GpuJoin *)h;
-    if (join_check_err(o)) return 1;
-    int nv = side == 0 ? o->cfg.n_left_vals : o->cfg.n_right_vals;
-    int ncols = o->cfg.n_keys + nv + 1;
-    std::vector<uint64_t> tags(o->I);
-    std::vector<unsigned long long> cur(o->I);
-    JHIP(o, hipMemcpyAsync(tags.data(), o->tag, (size_t)o->I * 8,
-                           hipMemcpyDeviceToHost, o->stream));
-    JHIP(o, hipMemcpyAsync(cur.data(), o->cursor[side], (size_t)o->I * 8,
-                           hipMemcpyDeviceToHost, o->stream));
-    JHIP(o, hipStreamSynchronize(o->stream));
-    int64_t total = 0;
-    for (uint32_t s = 0; s < o->I; s++)
-        if (tags[s] != EMPTY_TAG) total += (int64_t)cur[s];
-    memset(out, 0, sizeof *out);
-    out->n_rows = total;
-    out->n_cols = ncols;
-    out->cols = (void **)calloc(ncols, sizeof(void *));
-    out->is_f64 = (int32_t *)calloc(ncols, sizeof(int32_t));
-    for (int i = 0; i < ncols; i++)
-        out->cols[i] = malloc((size_t)(total ? total : 1) * 8);
-    size_t plane = (size_t)o->I * o->cap;
-    int64_t r = 0;
-    for (uint32_t s = 0; s < o->I; s++) {
-        if (tags[s] == EMPTY_TAG || cur[s] == 0) continue;
-        int64_t n = (int64_t)cur[s];
-        int col = 0;
-        if (o->cfg.n_keys) {
-            JHIP(o, hipMemcpyAsync((int64_t *)out->cols[col] + r,
-                                   o->key[side] + (size_t)s * o->cap,
-                                   (size_t)n * 8, hipMemcpyDeviceToHost,
-                                   o->stream));
-            col++;
-        }
-        for (int v = 0; v < nv; v++, col++)
-            JHIP(o, hipMemcpyAsync(
-                        (int64_t *)out->cols[col] + r,
-                        o->vals[side] + (size_t)v * plane + (size_t)s * o->cap,
-                        (size_t)n * 8, hipMemcpyDeviceToHost, o->stream));
-        JHIP(o, hipStreamSynchronize(o->stream));
-        for (int64_t j = 0; j < n; j++)
-            ((int64_t *)out->cols[ncols - 1])[r + j] = (int64_t)tags[s];
-        r += n;
-    }
-    return 0;
-}
-
-API void arroyo_amd_join_destroy(void *h) {
-    GpuJoin *o = (GpuJoin *)h;
-    if (!o) return;
-    hipStreamSynchronize(o->stream);
-    hipFree(o->tag);
-    for (int s = 0; s < 2; s++) {
-        hipFree(o->cursor[s]);
-        hipFree(o->key[s]);
-        hipFree(o->vals[s]);
-        int nc = o->cfg.n_keys +
-                 (s == 0 ? o->cfg.n_left_vals : o->cfg.n_right_vals) + 1;
-        for (int c = 0; c < nc; c++) {
-            hipHostFree(o->stg[s][c]);
-            hipFree(o->stg_d[s][c]);
-        }
-    }
-    hipFree(o->b_keys);
-    hipFree(o->b_head);
-    hipFree(o->b_next);
-    hipFree(o->l_hit);
-    for (int i = 0; i < o->out_cols && i < 16; i++) hipFree(o->d_out[i]);
-    hipFree(o->d_n_out);
-    hipFree(o->d_err);
-    hipStreamDestroy(o->stream);
-    delete o;
 }

@@ -15,7 +15,7 @@ from arroyo_amd.cabi import AmdOutBatch, WindowOp, _out_to_numpy
 _DIR = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_DIR, "libarroyo_amd.so")
 _SRCS = [os.path.join(_DIR, "csrc", f)
-         for f in ("arroyo_amd.hip", "session.hip", "expjoin.hip",
+         for f in ("arroyo_amd.hip", "join.hip", "session.hip", "expjoin.hip",
                    "updagg.hip", "windowfn.hip", "mapop.hip", "strkey.hip")]
 
 _lib = None

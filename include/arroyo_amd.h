@@ -127,8 +127,8 @@ void arroyo_amd_free_out(AmdOutBatch *out);
 void arroyo_amd_destroy(void *h);
 const char *arroyo_amd_last_error(void *h);
 
-/* Dominant-kernel timing for the measurement harness: total k_update time
- * (HIP events on the operator's stream), rows processed, launches, and rows
+/* Dominant-kernel timing for the measurement harness: total update-kernel
+ * time (HIP events on the operator's stream), rows processed, launches, and rows
  * emitted device-side since the last call. */
 int arroyo_amd_perf(void *h, double *update_ms, int64_t *rows,
                     int64_t *launches, int64_t *emitted_device_rows);

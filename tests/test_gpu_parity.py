@@ -58,9 +58,9 @@ def run_both(cols, lateness=NS, batch=65536, **kw):
     return got, want
 
 
-@pytest.mark.parametrize("use_lds", ["0", "1"])
-def test_q5_sliding_count_by_auction(use_lds, monkeypatch):
-    monkeypatch.setenv("ARROYO_AMD_LDS", use_lds)
+@pytest.mark.parametrize("upd", ["lds", "tile"])
+def test_q5_sliding_count_by_auction(upd, monkeypatch):
+    monkeypatch.setenv("ARROYO_AMD_UPD", upd)
     cols = nexmark.bids(500_000, events_per_sec=50_000)
     got, want = run_both(cols, width_ns=10 * NS, slide_ns=2 * NS, n_keys=1,
                          n_value_cols=0, aggs=[(cabi.COUNT, -1)],

@@ -3,7 +3,8 @@ keyed single-COUNT shape) against the CPU oracle, bit-exact, on the shapes
 where a per-block LDS table over a contiguous row span can go wrong: partial
 sub-tiles and spans, table overflow, a full probe bucket, a pane boundary
 inside a tile, sentinel keys and late rows.  Every case also runs with
-ARROYO_AMD_UPD=batch (k_update_batch_n) on the same steps."""
+ARROYO_AMD_UPD=batch (k_update_batch_n) and ARROYO_AMD_UPD=lds
+(k_update_lds_vec / k_update_lds) on the same steps."""
 import functools
 
 import numpy as np
@@ -18,7 +19,7 @@ pytestmark = pytest.mark.gpu
 T0 = 1_600_000_000 * NS          # a multiple of the 2 s slide
 SLIDE = 2 * NS
 RING_PANES = 16
-UPD = ["tile", "batch"]
+UPD = ["tile", "batch", "lds"]
 
 
 def config(log2_capacity):
@@ -100,7 +101,7 @@ def lds_home(key, pane, slots):
     return (hash64(x) & np.uint64(slots - 1)).astype(np.int64)
 
 
-# -- cases (oracle result computed once, shared by both kernels) -----------
+# -- cases (oracle result computed once, shared by all kernels) ------------
 
 @functools.lru_cache(maxsize=None)
 def case_odd_rows(n):
@@ -189,7 +190,8 @@ def test_forced_block_counts(blocks, upd, monkeypatch):
     check(case_forced_blocks(), upd, monkeypatch, blocks=blocks)
 
 
-@pytest.mark.parametrize("upd", UPD)
+# the lds kernel has no rows-per-thread knob, so it has no case here
+@pytest.mark.parametrize("upd", ["tile", "batch"])
 @pytest.mark.parametrize("bq", [12, 16])
 def test_wider_rows_per_thread(bq, upd, monkeypatch):
     # ARROYO_AMD_BQ keeps its meaning under both kernels; 10,007 rows leave
