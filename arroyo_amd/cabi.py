@@ -1447,3 +1447,83 @@ class StrKeyDict:
             self.close()
         except Exception:
             pass
+
+
+# ---- keyed shuffle: stable device partition (arroyo_amd_shuffle_*) --------
+
+AMD_SHUF_KEY_I64 = 0    # owner from splitmix64 of the key column
+AMD_SHUF_KEY_HASH = 1   # the key column already is a 64-bit hash
+AMD_SHUF_MAX_COLS = 16
+AMD_SHUF_MAX_PARTS = 64
+AMD_SHUF_MAX_ROWS = 1 << 30
+AMD_SHUF_N_KERNELS = 5
+AMD_SHUF_TILE_ROWS = 1024
+SHUF_KERNEL_NAMES = ("count", "scan", "scatter", "utf8_offsets", "utf8_copy")
+
+
+class AmdShuffleConfig(ctypes.Structure):
+    _fields_ = [
+        ("device", ctypes.c_int32),
+        ("n_parts", ctypes.c_int32),
+        ("n_cols", ctypes.c_int32),
+        ("key_col", ctypes.c_int32),
+        ("key_mode", ctypes.c_int32),
+        ("has_utf8", ctypes.c_int32),
+        ("max_rows", ctypes.c_int64),
+        ("max_bytes", ctypes.c_int64),
+    ]
+
+
+class AmdShuffleOut(ctypes.Structure):
+    _fields_ = [
+        ("n_rows", ctypes.c_int64),
+        ("cols", ctypes.c_void_p * AMD_SHUF_MAX_COLS),
+        ("utf8_offsets", ctypes.c_void_p),
+        ("utf8_data", ctypes.c_void_p),
+        ("row_start", ctypes.c_int64 * (AMD_SHUF_MAX_PARTS + 1)),
+        ("byte_start", ctypes.c_int64 * (AMD_SHUF_MAX_PARTS + 1)),
+    ]
+
+
+def make_shuffle_config(n_parts, n_cols, key_col=0, key_mode=AMD_SHUF_KEY_I64,
+                        has_utf8=False, max_rows=1 << 20, max_bytes=0,
+                        device=0):
+    cfg = AmdShuffleConfig()
+    cfg.device = device
+    cfg.n_parts = n_parts
+    cfg.n_cols = n_cols
+    cfg.key_col = key_col
+    cfg.key_mode = key_mode
+    cfg.has_utf8 = 1 if has_utf8 else 0
+    cfg.max_rows = max_rows
+    cfg.max_bytes = max_bytes
+    return cfg
+
+
+def bind_shuffle(lib, prefix="arroyo_amd_"):
+    """ctypes prototypes of the shuffle family; returns {name: function}."""
+    p = prefix + "shuffle_"
+    vp = ctypes.c_void_p
+    fn = {}
+    fn["create"] = getattr(lib, p + "create")
+    fn["create"].restype = vp
+    fn["create"].argtypes = [ctypes.POINTER(AmdShuffleConfig)]
+    fn["partition_device"] = getattr(lib, p + "partition_device")
+    fn["partition_device"].restype = ctypes.c_int
+    fn["partition_device"].argtypes = [
+        vp, ctypes.POINTER(vp), vp, vp, ctypes.c_int64,
+        ctypes.POINTER(AmdShuffleOut)]
+    fn["bind_output"] = getattr(lib, p + "bind_output")
+    fn["bind_output"].restype = ctypes.c_int
+    fn["bind_output"].argtypes = [vp, ctypes.POINTER(vp), vp, vp]
+    fn["profile"] = getattr(lib, p + "profile")
+    fn["profile"].restype = ctypes.c_int
+    fn["profile"].argtypes = [vp, ctypes.c_int, ctypes.c_int32,
+                              ctypes.POINTER(ctypes.c_double)]
+    fn["destroy"] = getattr(lib, p + "destroy")
+    fn["destroy"].restype = None
+    fn["destroy"].argtypes = [vp]
+    fn["last_error"] = getattr(lib, p + "last_error")
+    fn["last_error"].restype = ctypes.c_char_p
+    fn["last_error"].argtypes = [vp]
+    return fn

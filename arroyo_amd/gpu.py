@@ -16,7 +16,8 @@ _DIR = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_DIR, "libarroyo_amd.so")
 _SRCS = [os.path.join(_DIR, "csrc", f)
          for f in ("arroyo_amd.hip", "join.hip", "session.hip", "expjoin.hip",
-                   "updagg.hip", "windowfn.hip", "mapop.hip", "strkey.hip")]
+                   "updagg.hip", "windowfn.hip", "mapop.hip", "strkey.hip",
+                   "shuffle.hip")]
 
 _lib = None
 
@@ -190,3 +191,121 @@ def make_map_op(cfg):
 def make_strkey(cfg):
     from arroyo_amd.cabi import StrKeyDict
     return StrKeyDict(lib(), "arroyo_amd_", cfg)
+
+
+class Shuffler:
+    """Stable device partition for the keyed shuffle (arroyo_amd_shuffle_*):
+    up to 16 8-byte columns and optionally one Arrow Utf8 column, split
+    into n_parts contiguous segments, rows of a segment in input order.
+
+    With bind_output (the default) the results land in torch tensors this
+    wrapper allocates once and binds to the handle, so partition() returns
+    ordinary torch views that an exchange may send as they are.  Without it
+    only partition_ptrs() is available and the results stay in the handle's
+    own buffers, for chaining into another handle's *_device call."""
+
+    def __init__(self, cfg, bind_output=True):
+        from arroyo_amd.cabi import bind_shuffle
+        self._fn = bind_shuffle(lib())
+        self.cfg = cfg
+        self._h = self._fn["create"](ctypes.byref(cfg))
+        if not self._h:
+            raise RuntimeError("arroyo_amd_shuffle_create failed: " +
+                               self._fn["last_error"](None).decode())
+        self._out = None
+        if bind_output:
+            import torch
+            dev = torch.device("cuda", cfg.device)
+            cols = [torch.empty(cfg.max_rows, dtype=torch.int64, device=dev)
+                    for _ in range(cfg.n_cols)]
+            off = data = None
+            if cfg.has_utf8:
+                off = torch.empty(cfg.max_rows + cfg.n_parts,
+                                  dtype=torch.int32, device=dev)
+                data = torch.empty(max(cfg.max_bytes, 1), dtype=torch.uint8,
+                                   device=dev)
+            arr = (ctypes.c_void_p * cfg.n_cols)(*[c.data_ptr() for c in cols])
+            self._check(self._fn["bind_output"](
+                self._h, arr, off.data_ptr() if cfg.has_utf8 else None,
+                data.data_ptr() if cfg.has_utf8 else None))
+            self._out = (cols, off, data)
+
+    def _check(self, rc):
+        if rc != 0:
+            raise RuntimeError(self._fn["last_error"](self._h).decode())
+
+    def partition_ptrs(self, dev_ptrs, n_rows, d_offsets=None, d_data=None):
+        """Device addresses (ints, None = NULL) in, AmdShuffleOut out; its
+        device pointers are valid until the next call on this handle."""
+        from arroyo_amd.cabi import AmdShuffleOut
+        arr = (ctypes.c_void_p * len(dev_ptrs))(*dev_ptrs)
+        out = AmdShuffleOut()
+        self._check(self._fn["partition_device"](
+            self._h, arr, d_offsets, d_data, n_rows, ctypes.byref(out)))
+        return out
+
+    def partition(self, cols, utf8=None):
+        """cols: n_cols equal-length contiguous 8-byte torch tensors on the
+        handle's device; utf8: (int32 offsets [n + 1], uint8 data) tensors
+        or None.  Returns shuffle.Partitioned whose tensors are views of
+        this wrapper's output tensors, valid until the next call."""
+        import torch
+        from arroyo_amd.shuffle import Partitioned
+        if self._out is None:
+            raise RuntimeError("partition() needs bind_output=True")
+        if len(cols) != self.cfg.n_cols:
+            raise ValueError(f"expected {self.cfg.n_cols} columns")
+        n = cols[0].numel()
+        for c in cols:
+            if c.numel() != n or c.element_size() != 8 or \
+                    not c.is_contiguous() or not c.is_cuda:
+                raise ValueError("columns must be equal-length contiguous "
+                                 "8-byte device tensors")
+        d_off = d_data = None
+        if utf8 is not None:
+            off, data = utf8
+            if off.dtype != torch.int32 or off.numel() != n + 1 or \
+                    data.dtype != torch.uint8 or not off.is_contiguous() or \
+                    not data.is_contiguous():
+                raise ValueError("utf8 = (int32 offsets [n + 1], uint8 data)")
+            # a column of empty strings may come with a zero-size data
+            # tensor; no byte is read then, any non-NULL address will do
+            d_off, d_data = off.data_ptr(), data.data_ptr() or off.data_ptr()
+        # fence torch's stream before the handle's own stream reads
+        torch.cuda.current_stream(cols[0].device).synchronize()
+        out = self.partition_ptrs([c.data_ptr() for c in cols], n, d_off,
+                                  d_data)
+        k = self.cfg.n_parts
+        ocols, ooff, odata = self._out
+        views = [ocols[i][:n].view(cols[i].dtype) for i in range(len(cols))]
+        if utf8 is None:
+            return Partitioned(views, out.row_start[:k + 1])
+        return Partitioned(views, out.row_start[:k + 1], ooff[:n + k],
+                           odata[:out.byte_start[k]], out.byte_start[:k + 1])
+
+    def profile(self, enable=None, copy_threshold=None):
+        """Measurement aid: switch per-kernel event timing on/off and set the
+        byte-copy threshold (None leaves either); returns the kernel
+        milliseconds of the last timed call by kernel name."""
+        from arroyo_amd.cabi import AMD_SHUF_N_KERNELS, SHUF_KERNEL_NAMES
+        ms = (ctypes.c_double * AMD_SHUF_N_KERNELS)()
+        self._check(self._fn["profile"](
+            self._h, -1 if enable is None else int(bool(enable)),
+            -1 if copy_threshold is None else int(copy_threshold), ms))
+        return dict(zip(SHUF_KERNEL_NAMES, ms))
+
+    def close(self):
+        if self._h:
+            self._fn["destroy"](self._h)
+            self._h = None
+            self._out = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def make_shuffler(cfg, bind_output=True):
+    return Shuffler(cfg, bind_output)

@@ -44,6 +44,130 @@ def partition_ids(keys, n_parts):
     return (h // range_size).astype(np.int64)
 
 
+KEY_I64 = 0    # cabi.AMD_SHUF_KEY_I64: owner from splitmix64 of the key column
+KEY_HASH = 1   # cabi.AMD_SHUF_KEY_HASH: the key column already is a hash
+
+
+def owners_device_rule(h, n_parts):
+    """Owner per 64-bit hash by the device rule (k_partition and the
+    arroyo_amd_shuffle_* family): range = UINT64_MAX // n_parts + 1,
+    owner = h // range, owner = 0 for one partition.  Unlike partition_ids'
+    2**64 // n_parts this never yields owner == n_parts."""
+    h = np.asarray(h, dtype=np.uint64)
+    if n_parts == 1:
+        return np.zeros(len(h), dtype=np.int64)
+    return (h // U64((2**64 - 1) // n_parts + 1)).astype(np.int64)
+
+
+class Partitioned:
+    """A batch split into n_parts contiguous segments, rows of a segment in
+    input order: the layout of AmdShuffleOut.  cols, utf8_offsets and
+    utf8_data are numpy arrays (partition_host) or torch device tensors
+    (gpu.Shuffler.partition); row_start and byte_start are host int lists
+    of n_parts + 1 entries."""
+
+    def __init__(self, cols, row_start, utf8_offsets=None, utf8_data=None,
+                 byte_start=None):
+        self.cols = cols
+        self.row_start = [int(x) for x in row_start]
+        self.utf8_offsets = utf8_offsets
+        self.utf8_data = utf8_data
+        self.byte_start = [int(x) for x in byte_start] \
+            if byte_start is not None else [0] * len(self.row_start)
+        self.n_parts = len(self.row_start) - 1
+
+    def count(self, p):
+        return self.row_start[p + 1] - self.row_start[p]
+
+    def part_cols(self, p):
+        lo, hi = self.row_start[p], self.row_start[p + 1]
+        return [c[lo:hi] for c in self.cols]
+
+    def part_utf8(self, p):
+        """Partition p's strings as a standalone Arrow Utf8 array:
+        (count + 1 offsets starting at 0, its bytes)."""
+        if self.utf8_offsets is None:
+            return None
+        lo, hi = self.row_start[p] + p, self.row_start[p + 1] + p + 1
+        return (self.utf8_offsets[lo:hi],
+                self.utf8_data[self.byte_start[p]:self.byte_start[p + 1]])
+
+
+def partition_host(cols, key_col, key_mode, n_parts, utf8=None):
+    """numpy restatement of arroyo_amd_shuffle_partition_device: device owner
+    rule, then a stable argsort.  cols: equal-length 8-byte numpy columns;
+    utf8: (int32 offsets [n + 1], uint8 data) or None.  The checker for the
+    kernels and the CPU path of shuffle_batch."""
+    cols = [np.ascontiguousarray(c) for c in cols]
+    for c in cols:
+        if c.dtype.itemsize != 8:
+            raise ValueError("shuffle columns are 8-byte elements")
+    key = cols[key_col].view(np.uint64)
+    with np.errstate(over="ignore"):
+        h = key if key_mode == KEY_HASH else splitmix64_np(key)
+    owner = owners_device_rule(h, n_parts)
+    order = np.argsort(owner, kind="stable")
+    row_start = np.zeros(n_parts + 1, dtype=np.int64)
+    np.cumsum(np.bincount(owner, minlength=n_parts), out=row_start[1:])
+    out_cols = [c[order] for c in cols]
+    if utf8 is None:
+        return Partitioned(out_cols, row_start)
+    offsets = np.asarray(utf8[0]).astype(np.int64)
+    data = np.asarray(utf8[1], dtype=np.uint8)
+    if len(offsets) != len(order) + 1:
+        raise ValueError("offsets needs n_rows + 1 entries")
+    lens = np.diff(offsets)
+    if offsets[0] < 0 or (lens < 0).any():
+        raise ValueError("malformed offsets: negative or decreasing")
+    lens = lens[order]
+    pos = np.zeros(len(order) + 1, dtype=np.int64)   # destination byte of row
+    np.cumsum(lens, out=pos[1:])
+    byte_start = pos[row_start]
+    out_off = np.empty(len(order) + n_parts, dtype=np.int32)
+    for p in range(n_parts):
+        lo, hi = row_start[p], row_start[p + 1]
+        out_off[lo + p:hi + p + 1] = pos[lo:hi + 1] - byte_start[p]
+    src = np.repeat(offsets[:-1][order] - pos[:-1], lens) + \
+        np.arange(pos[-1], dtype=np.int64)
+    return Partitioned(out_cols, row_start, out_off, data[src], byte_start)
+
+
+def shuffle_batch(cols, key_col, key_mode, n_parts, utf8=None, group=None,
+                  partitioner=None):
+    """Stable keyed exchange of one batch: partition (partitioner.partition,
+    a gpu.Shuffler, on torch device tensors; partition_host on numpy columns
+    otherwise), then all_to_all_tensors per column and, with utf8, for the
+    offsets and the bytes.  Returns what was received PER SOURCE RANK, in
+    rank order, as a list of (cols, utf8) with utf8 = (offsets, data) or
+    None: every source's rows stay in its order, so the result does not
+    depend on arrival order."""
+    world = dist.get_world_size(group)
+    assert world == n_parts
+    if partitioner is not None:
+        part = partitioner.partition(cols, utf8)
+        # RCCL sends the device segments as they are; any other backend
+        # (gloo) gets host copies
+        if dist.get_backend(group) == "nccl":
+            as_tensor = lambda x: x
+        else:
+            as_tensor = lambda x: x.cpu()
+    else:
+        part = partition_host(cols, key_col, key_mode, n_parts, utf8)
+        as_tensor = lambda x: torch.from_numpy(np.ascontiguousarray(x))
+    recv_cols = []
+    for c in range(len(part.cols)):
+        recv_cols.append(all_to_all_tensors(
+            [as_tensor(part.part_cols(p)[c]) for p in range(n_parts)], group))
+    recv_off = recv_data = None
+    if part.utf8_offsets is not None:
+        segs = [part.part_utf8(p) for p in range(n_parts)]
+        recv_off = all_to_all_tensors([as_tensor(s[0]) for s in segs], group)
+        recv_data = all_to_all_tensors([as_tensor(s[1]) for s in segs], group)
+    return [([rc[src] for rc in recv_cols],
+             (recv_off[src], recv_data[src]) if recv_off is not None else None)
+            for src in range(world)]
+
+
 def recv_splits_of(gathered_flat, world, rank):
     """Decode an all-gathered [world x world] send-split matrix (row =
     sender, column = destination) into this rank's receive splits, indexed

@@ -452,6 +452,74 @@ void arroyo_amd_strkey_free_out(AmdStrBatch *out);
 void arroyo_amd_strkey_destroy(void *h);
 const char *arroyo_amd_strkey_last_error(void *h);
 
+/* ---- keyed shuffle: stable device partition ------------------------------
+ * The reference repartitions a batch between subtasks by sorting it by
+ * destination and slicing (crates/arroyo-operator/src/context.rs:506-560);
+ * the destination is the contiguous range of the key hash
+ * (server_for_hash, crates/arroyo-types/src/lib.rs:640-647).  This family is
+ * the device side of that: it splits a batch of up to AMD_SHUF_MAX_COLS
+ * 8-byte columns, and optionally one Arrow Utf8 column, into n_parts
+ * contiguous segments that can be handed to the exchange as they are.
+ *
+ * Owner rule: range = UINT64_MAX / n_parts + 1, owner = h / range, and
+ * owner = 0 when n_parts == 1 -- the rule of arroyo_amd_partition.  h is
+ * splitmix64 of the key column (AMD_SHUF_KEY_I64) or the key column itself
+ * (AMD_SHUF_KEY_HASH, for the strkey content hash).
+ *
+ * Stable: inside a partition the rows keep their input order, and the output
+ * is a pure function of the input.  An updating stream (is_retract rows)
+ * relies on this: a key's append and its retraction reach the owner in the
+ * order they were produced.  arroyo_amd_partition does not promise it.
+ *
+ * Utf8: d_offsets holds n_rows + 1 int32 entries and offsets[0] may be
+ * non-zero.  A negative or decreasing offset is an error, detected on the
+ * device before any byte of d_data is read; no byte outside
+ * [offsets[0], offsets[n_rows]) is read.  Every partition comes out as a
+ * standalone Utf8 array (see AmdShuffleOut), so a segment can be shipped and
+ * passed to arroyo_amd_strkey_encode_device on the receiver without rebasing.
+ * The empty string, embedded NUL bytes and non-UTF-8 bytes are legal.
+ *
+ * Errors (non-zero return, message in shuffle_last_error; the handle stays
+ * usable and `out` is undefined): n_rows above max_rows, Utf8 bytes above
+ * max_bytes, malformed offsets, a NULL column pointer, has_utf8 with a NULL
+ * offsets or data pointer.  n_rows == 0 is legal: all starts are 0, every
+ * partition is an empty Utf8 array and no input pointer is read.
+ *
+ * A call allocates no device memory and never synchronises the device: the
+ * kernels run on the handle's own stream, which is synchronised once before
+ * returning, so a chained *_process_batch_device or strkey_encode_device on
+ * another handle may consume the outputs directly.  One call at a time per
+ * handle.
+ *
+ * Out of scope: more than one Utf8 column; LargeUtf8 (int64 offsets);
+ * validity bitmaps (a bitmap column can ride along only once widened to an
+ * 8-byte column).  arroyo_amd_partition is unchanged and nothing switches
+ * over to this family silently. */
+void *arroyo_amd_shuffle_create(const AmdShuffleConfig *cfg);
+int arroyo_amd_shuffle_partition_device(void *h, const int64_t *const *dcols,
+                                        const int32_t *d_offsets,
+                                        const uint8_t *d_data, int64_t n_rows,
+                                        AmdShuffleOut *out);
+/* Route the results of later calls into caller-owned device buffers, for an
+ * exchange layer that must own the memory it sends (a torch.distributed
+ * all-to-all, say): n_cols columns of max_rows entries each and, with
+ * has_utf8, max_rows + n_parts offsets and max_bytes data bytes.  The
+ * pointers in AmdShuffleOut are then these buffers.  d_out_cols == NULL
+ * returns to the handle's own buffers, which stay allocated either way. */
+int arroyo_amd_shuffle_bind_output(void *h, int64_t *const *d_out_cols,
+                                   int32_t *d_out_offsets,
+                                   uint8_t *d_out_data);
+/* Measurement aid: enable > 0 makes every later call time its kernels with
+ * HIP events, enable == 0 stops that, enable < 0 leaves the setting.
+ * copy_threshold >= 0 sets the string length up to which the byte copy uses
+ * one lane per string (0: the whole wave copies every string; INT32_MAX: one
+ * lane per string always); < 0 leaves it.  last_kernel_ms (may be NULL)
+ * receives AMD_SHUF_N_KERNELS kernel times of the last timed call. */
+int arroyo_amd_shuffle_profile(void *h, int enable, int32_t copy_threshold,
+                               double *last_kernel_ms);
+void arroyo_amd_shuffle_destroy(void *h);
+const char *arroyo_amd_shuffle_last_error(void *h);
+
 #ifdef __cplusplus
 }
 #endif

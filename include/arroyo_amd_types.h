@@ -392,6 +392,51 @@ typedef struct {
     uint8_t *data;           /* [offsets[n_rows]] */
 } AmdStrBatch;
 
+/* Device keyed shuffle (arroyo_amd_shuffle_*): the stable partition ahead of
+ * the cross-rank exchange (the reference's repartition, crates/
+ * arroyo-operator/src/context.rs:506-560).  Every device buffer of a handle
+ * is sized at create from max_rows / max_bytes; a call allocates nothing. */
+#define AMD_SHUF_KEY_I64  0  /* owner = hash64(cols[key_col]) / range, the
+                              * splitmix64 + range rule of arroyo_amd_partition */
+#define AMD_SHUF_KEY_HASH 1  /* cols[key_col] already is a 64-bit hash (the
+                              * strkey content hash), used as is */
+#define AMD_SHUF_MAX_COLS 16
+#define AMD_SHUF_MAX_PARTS 64
+#define AMD_SHUF_MAX_ROWS (1LL << 30)
+#define AMD_SHUF_N_KERNELS 5 /* count, scan, scatter, utf8 offsets, utf8 copy */
+#define AMD_SHUF_TILE_ROWS 1024 /* consecutive rows one block counts and
+                                 * scatters; sizes around it are the edge
+                                 * cases of the kernels */
+
+typedef struct {
+    int32_t device;
+    int32_t n_parts;         /* 1..AMD_SHUF_MAX_PARTS */
+    int32_t n_cols;          /* 8-byte columns carried (i64, u64 or f64 bit
+                              * patterns), 1..AMD_SHUF_MAX_COLS, the key
+                              * column among them */
+    int32_t key_col;         /* 0..n_cols - 1 */
+    int32_t key_mode;        /* AMD_SHUF_KEY_* */
+    int32_t has_utf8;        /* 1: one Arrow Utf8 column rides along */
+    int64_t max_rows;        /* rows per call, 1..AMD_SHUF_MAX_ROWS */
+    int64_t max_bytes;       /* Utf8 bytes per call, 0..INT32_MAX */
+} AmdShuffleConfig;
+
+/* Result of one partition call.  The pointers are device memory owned by the
+ * handle, valid until the next call on it; the starts are host values.
+ * Partition p is rows [row_start[p], row_start[p + 1]) of every column, in
+ * input order.  Its strings are a standalone Arrow Utf8 array: the
+ * row_start[p + 1] - row_start[p] + 1 offsets from index row_start[p] + p of
+ * utf8_offsets (the first is 0), relative to utf8_data + byte_start[p]; its
+ * bytes are [byte_start[p], byte_start[p + 1]). */
+typedef struct {
+    int64_t  n_rows;
+    int64_t *cols[AMD_SHUF_MAX_COLS];
+    int32_t *utf8_offsets;   /* n_rows + n_parts entries */
+    uint8_t *utf8_data;
+    int64_t  row_start[AMD_SHUF_MAX_PARTS + 1];
+    int64_t  byte_start[AMD_SHUF_MAX_PARTS + 1];
+} AmdShuffleOut;
+
 #ifdef __cplusplus
 }
 #endif
