@@ -41,28 +41,16 @@
  * Semantics are pinned bit-for-bit against oracle/arroyo_oracle.c (itself
  * pinned against the reference's golden vectors) by tests/test_gpu_parity.py.
  */
-#include <hip/hip_runtime.h>
-
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <algorithm>
 #include <map>
 #include <set>
 #include <string>
-#include <vector>
 
-#include "../../include/arroyo_amd_types.h"
-
-#define API extern "C" __attribute__((visibility("default")))
+#include "op_common.h"
 
 /* ------------------------------------------------------------------ */
 /* device-side layout                                                  */
 
-#define EMPTY_KEY  (-1LL)          /* all-0xFF bytes: memset-clearable */
-#define EMPTY_TAG  (~0ULL)
 #define ERR_RING_CONFLICT 2
-#define ERR_TABLE_FULL    3
 
 /* per-word merge ops over the encoded state domain */
 enum WordOp { W_ADD_I64 = 0, W_MAX_U64 = 1, W_ADD_F64 = 2, W_NONE = 3 };
@@ -152,13 +140,6 @@ __device__ inline uint64_t div_slide(uint64_t t, uint64_t slide,
     return q;
 }
 
-__device__ inline uint64_t hash64(uint64_t x) {
-    x += 0x9e3779b97f4a7c15ULL;
-    x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ULL;
-    x = (x ^ (x >> 27)) * 0x94d049bb133111ebULL;
-    return x ^ (x >> 31);
-}
-
 /* fold one input row into an encoded state vector via atomics */
 __device__ inline void atomic_update(uint64_t *st, const AggSpec a,
                                      const int64_t *const *vcols, int64_t r) {
@@ -230,35 +211,6 @@ __device__ inline void atomic_merge(uint64_t *dst, const uint64_t *src,
             break;
         }
     }
-}
-
-/* claim-or-find a key slot in an open-addressing table.
- * Keys transition EMPTY->k exactly once, so the plain-load fast path is
- * safe: a stale L1 read can only see EMPTY, and the CAS resolves it.
- * Fullness is detected by probe length (expected probe count at <=7/8 load
- * is single digits; a 256-probe chain means the table is effectively full).
- * No per-insert fill counter: a same-address atomicAdd per insert was
- * serializing at the L2 bank. */
-#define MAX_PROBES 256u
-
-__device__ inline int64_t table_upsert(int64_t *keys, uint32_t C, int64_t key,
-                                       int *err) {
-    uint64_t m = C - 1;
-    uint64_t i = hash64((uint64_t)key) & m;
-    uint32_t lim = C < MAX_PROBES ? C : MAX_PROBES;
-    for (uint32_t probes = 0; probes < lim; probes++) {
-        int64_t k = keys[i];
-        if (k == key) return (int64_t)i;
-        if (k == EMPTY_KEY) {
-            int64_t old = (int64_t)atomicCAS((unsigned long long *)&keys[i],
-                                             (unsigned long long)EMPTY_KEY,
-                                             (unsigned long long)key);
-            if (old == EMPTY_KEY || old == key) return (int64_t)i;
-        }
-        i = (i + 1) & m;
-    }
-    *err = ERR_TABLE_FULL;
-    return -1;
 }
 
 /* claim a pane's ring slot for `bin`; wave-cooperative callers dedup first.
@@ -1914,24 +1866,6 @@ k_scatter(const uint32_t *part_ids, unsigned long long *cursors,
 /* ------------------------------------------------------------------ */
 /* host side: operator handle + state machine                          */
 
-#define HIP_CHECK(op, call)                                                  \
-    do {                                                                     \
-        hipError_t _e = (call);                                              \
-        if (_e != hipSuccess) {                                              \
-            snprintf((op)->err_msg, sizeof (op)->err_msg, "%s:%d hip: %s",   \
-                     __FILE__, __LINE__, hipGetErrorString(_e));             \
-            return 1;                                                        \
-        }                                                                    \
-    } while (0)
-
-struct Staged {
-    /* pinned host staging for host-memory process_batch calls */
-    int64_t *buf[16];      /* key?, vcols..., ts (restore: key?, states...) */
-    int64_t  cap, n;
-    int64_t *dbuf[16];
-    int      ncols;
-};
-
 /* update kernel of an operator (ARROYO_AMD_UPD=lds|batch|tile) */
 enum UpdKind {
     UPD_LDS,    /* k_update_lds_vec / k_update_lds: every shape; the only
@@ -1941,7 +1875,7 @@ enum UpdKind {
     UPD_TILE,   /* k_update_tile: keyed single-COUNT, its default */
 };
 
-struct GpuOp {
+struct GpuOp : OpBase {
     AmdWindowConfig cfg;
     AggSpec agg;
     int n_in_cols;       /* n_keys + n_value_cols + 1 */
@@ -1979,7 +1913,6 @@ struct GpuOp {
     /* host-accumulated emission (emit_to_host) */
     std::vector<std::vector<int64_t>> host_out;
 
-    hipStream_t stream;
     /* fire path (pane close -> cpi build -> merge -> retire) runs on its
      * own stream, overlapping the NEXT periods' update kernels: both are
      * latency-bound (update 87.5% memory-parked, merge ~470 GB/s) so
@@ -2023,7 +1956,9 @@ struct GpuOp {
                                  reuse distance R/bins-per-group >> this) */
     std::vector<uint64_t> retired_bin;  /* [R] bin whose async retire may
                                            not yet show in d_status */
-    Staged stg;
+    /* pinned host staging for host-memory process_batch calls:
+     * key?, vcols..., ts (restore: key?, states...) */
+    Staging stg;
 
     /* one contiguous device status block [err, min_bin, tags[R]] mirrored
      * into pinned host memory: ONE copy + ONE sync per watermark instead of
@@ -2079,7 +2014,6 @@ struct GpuOp {
     int64_t  update_rows;
     int64_t  launches;
     int64_t  emitted_device_rows;
-    char err_msg[512];
 };
 
 #define EV_POOL 64
@@ -2105,8 +2039,6 @@ static void harvest_events(GpuOp *o, int block) {
     (void)hipGetLastError();   /* clear NotReady sticky */
     o->ev_inflight = std::move(keep);
 }
-
-static thread_local char g_err[512];
 
 /* order the fire stream after every update launched so far (one event) */
 static int gate_fire(GpuOp *o) {
@@ -2222,13 +2154,13 @@ API void *arroyo_amd_create(const AmdWindowConfig *cfg) {
     if (!cfg || cfg->n_aggs < 1 || cfg->n_aggs > AMD_MAX_AGGS ||
         cfg->n_keys < 0 || cfg->n_keys > 4 || cfg->width_nanos == 0 ||
         cfg->n_value_cols > 4) {
-        snprintf(g_err, sizeof g_err, "invalid config");
+        snprintf(g_create_err, sizeof g_create_err, "invalid config");
         return nullptr;
     }
     for (int i = 0; i < cfg->n_aggs; i++)
         if (cfg->agg_ops[i] >= AMD_AGG_MEDIAN &&
             cfg->agg_ops[i] <= AMD_AGG_MAX_RETRACT) {
-            snprintf(g_err, sizeof g_err,
+            snprintf(g_create_err, sizeof g_create_err,
                      "invalid config: aggregate op %d is updating-aggregate "
                      "only", cfg->agg_ops[i]);
             return nullptr;
@@ -2237,12 +2169,13 @@ API void *arroyo_amd_create(const AmdWindowConfig *cfg) {
         cfg->width_nanos % cfg->slide_nanos != 0) {
         /* the reference's planner rejects this (arroyo-planner/src/lib.rs
          * :644: "hop() width currently must be a multiple of slide") */
-        snprintf(g_err, sizeof g_err,
+        snprintf(g_create_err, sizeof g_create_err,
                  "hop() width must be a multiple of slide");
         return nullptr;
     }
     if (!cfg->is_tumbling && cfg->slide_nanos == 0) {
-        snprintf(g_err, sizeof g_err, "sliding window needs slide > 0");
+        snprintf(g_create_err, sizeof g_create_err,
+                 "sliding window needs slide > 0");
         return nullptr;
     }
     GpuOp *o = new GpuOp();
@@ -2293,7 +2226,7 @@ API void *arroyo_amd_create(const AmdWindowConfig *cfg) {
     if (const char *e = getenv("ARROYO_AMD_EVENTS")) o->use_events = atoi(e);
 
     if (hipSetDevice(cfg->device) != hipSuccess) {
-        snprintf(g_err, sizeof g_err,
+        snprintf(g_create_err, sizeof g_create_err,
                  "hipSetDevice(%d) failed: no HIP device (the arroyo-amd "
                  "product path requires a GPU; it never falls back to CPU)",
                  cfg->device);
@@ -2301,11 +2234,6 @@ API void *arroyo_amd_create(const AmdWindowConfig *cfg) {
         return nullptr;
     }
     size_t na = o->agg.n_aggs;
-    auto fail = [&](const char *what, hipError_t e) {
-        snprintf(g_err, sizeof g_err, "%s: %s", what, hipGetErrorString(e));
-        delete o;
-        return nullptr;
-    };
     /* update kernel: the keyed single-COUNT shape (the q5 headline) takes
      * the tile kernel by default and may be switched to "batch" or "lds";
      * every other shape always takes the LDS-staged kernel.  An unknown
@@ -2318,24 +2246,21 @@ API void *arroyo_amd_create(const AmdWindowConfig *cfg) {
         else if (count_shape && !strcmp(ev, "batch")) o->upd_kind = UPD_BATCH;
         else if (count_shape && !strcmp(ev, "tile")) o->upd_kind = UPD_TILE;
     }
-    hipError_t e;
-#define ALLOC(p, bytes)                                                      \
-    if ((e = hipMalloc((void **)&(p), (bytes))) != hipSuccess)               \
-        return fail(#p, e);
-    ALLOC(o->ring.keys, (size_t)o->ring.R * o->ring.C * 8);
-    ALLOC(o->ring.state, (size_t)o->ring.R * o->ring.C * na * 16);
-    ALLOC(o->d_status, (2 + (size_t)o->ring.R) * 8);
+    OP_ALLOC(o, o->ring.keys, (size_t)o->ring.R * o->ring.C * 8, 0xFF);
+    OP_ALLOC(o, o->ring.state, (size_t)o->ring.R * o->ring.C * na * 16, 0);
+    /* status block [err, min_bin, tags[R]]: err 0, the rest all-0xFF */
+    OP_ALLOC(o, o->d_status, (2 + (size_t)o->ring.R) * 8, 0xFF);
     o->ring.err = (int *)o->d_status;
     o->ring.min_bin = o->d_status + 1;
     o->ring.tag = o->d_status + 2;
-    if (hipHostMalloc((void **)&o->h_status,
-                      (2 + (size_t)o->ring.R) * 8) != hipSuccess)
-        return fail("h_status", hipErrorOutOfMemory);
-    ALLOC(o->ring.spec_used, (size_t)o->ring.R * 4);
-    ALLOC(o->ring.spec_state, (size_t)o->ring.R * na * 16);
-    ALLOC(o->m_keys, (size_t)o->CM * 8);
+    OP_TRY(o, "d_status", hipMemset(o->ring.err, 0, 4));
+    OP_TRY(o, "h_status",
+           o->pinned_alloc(o->h_status, (2 + (size_t)o->ring.R) * 8));
+    OP_ALLOC(o, o->ring.spec_used, (size_t)o->ring.R * 4, 0);
+    OP_ALLOC(o, o->ring.spec_state, (size_t)o->ring.R * na * 16, 0);
+    OP_ALLOC(o, o->m_keys, (size_t)o->CM * 8, 0xFF);
     o->m_zero_bytes = (size_t)o->CM * na * 16 + 8 + na * 16 + 8;
-    ALLOC(o->m_zero_blob, o->m_zero_bytes);
+    OP_ALLOC(o, o->m_zero_blob, o->m_zero_bytes, 0);
     o->m_state = o->m_zero_blob;
     o->m_spec_used =
         (uint32_t *)(o->m_zero_blob + (size_t)o->CM * na * 2);
@@ -2343,13 +2268,13 @@ API void *arroyo_amd_create(const AmdWindowConfig *cfg) {
     o->d_n_out = (unsigned long long *)(o->m_spec_state + na * 2);
     o->out_rows_cap = (int64_t)o->CM + 1;
     for (int i = 0; i < o->n_out_alloc; i++)
-        ALLOC(o->d_out[i], (size_t)o->out_rows_cap * 8);
+        OP_ALLOC(o, o->d_out[i], (size_t)o->out_rows_cap * 8);
     if (o->own_fstream)
         for (int i = 0; i < o->n_out_alloc; i++)
-            ALLOC(o->d_out2[i], (size_t)o->out_rows_cap * 8);
-    ALLOC(o->d_emitted, 8);
-    ALLOC(o->d_fire_cur, 64 * 8);
-    ALLOC(o->d_fire_cur2, 64 * 8);
+            OP_ALLOC(o, o->d_out2[i], (size_t)o->out_rows_cap * 8);
+    OP_ALLOC(o, o->d_emitted, 8, 0);
+    OP_ALLOC(o, o->d_fire_cur, 64 * 8, 0);
+    OP_ALLOC(o, o->d_fire_cur2, 64 * 8, 0);
     /* fused-merge home range fixed at create (CPI grouping depends on it) */
     o->mf_range = MF_RANGE;
     if (const char *ev = getenv("ARROYO_AMD_MF_RANGE"))
@@ -2377,9 +2302,9 @@ API void *arroyo_amd_create(const AmdWindowConfig *cfg) {
         if (use_cpi) {
             o->cpi_ew = (na == 1 && o->agg.op[0] != AMD_AGG_AVG)
                             ? 2 : (int)(1 + 2 * na);
-            ALLOC(o->cpi_entries,
-                  (size_t)o->ring.R * o->ring.C * o->cpi_ew * 8);
-            ALLOC(o->cpi_cnt, (size_t)o->ring.R * o->cpi_nr * 4);
+            OP_ALLOC(o, o->cpi_entries,
+                     (size_t)o->ring.R * o->ring.C * o->cpi_ew * 8);
+            OP_ALLOC(o, o->cpi_cnt, (size_t)o->ring.R * o->cpi_nr * 4);
         }
     }
     o->cpi_ready.assign(o->ring.R, 0);
@@ -2388,32 +2313,19 @@ API void *arroyo_amd_create(const AmdWindowConfig *cfg) {
         /* dictionary 4x the pane table; ids must stay stable, so no
          * eviction — exhaustion is a loud ERR_DICT_FULL */
         o->dict_D = o->ring.C << 2;
-        ALLOC(o->d_dict_digest, (size_t)o->dict_D * 8);
-        ALLOC(o->d_dict_keys, (size_t)o->dict_D * o->cfg.n_keys * 8);
-        ALLOC(o->d_dict_ready, (size_t)o->dict_D * 4);
-        ALLOC(o->d_keyid_out, (size_t)o->out_rows_cap * 8);
-        hipMemset(o->d_dict_digest, 0xFF, (size_t)o->dict_D * 8);
-        hipMemset(o->d_dict_ready, 0, (size_t)o->dict_D * 4);
+        OP_ALLOC(o, o->d_dict_digest, (size_t)o->dict_D * 8, 0xFF);
+        OP_ALLOC(o, o->d_dict_keys, (size_t)o->dict_D * o->cfg.n_keys * 8);
+        OP_ALLOC(o, o->d_dict_ready, (size_t)o->dict_D * 4, 0);
+        OP_ALLOC(o, o->d_keyid_out, (size_t)o->out_rows_cap * 8);
     }
-#undef ALLOC
-    hipMemset(o->ring.keys, 0xFF, (size_t)o->ring.R * o->ring.C * 8);
-    hipMemset(o->ring.state, 0, (size_t)o->ring.R * o->ring.C * na * 16);
-    hipMemset(o->ring.tag, 0xFF, (size_t)o->ring.R * 8);
-    hipMemset(o->ring.spec_used, 0, (size_t)o->ring.R * 4);
-    hipMemset(o->ring.spec_state, 0, (size_t)o->ring.R * na * 16);
-    hipMemset(o->ring.err, 0, 4);
-    hipMemset(o->ring.min_bin, 0xFF, 8);
-    hipMemset(o->m_keys, 0xFF, (size_t)o->CM * 8);
-    hipMemset(o->m_zero_blob, 0, o->m_zero_bytes);
-    hipMemset(o->d_emitted, 0, 8);
-    hipMemset(o->d_fire_cur, 0, 64 * 8);
-    hipMemset(o->d_fire_cur2, 0, 64 * 8);
     o->fire_seq = o->fire_seq2 = 0;
     /* the update stream paces the period: give it scheduler priority over
      * the fire streams so its blocks win the CU race (fires have slack) */
     int pr_lo = 0, pr_hi = 0;
-    hipDeviceGetStreamPriorityRange(&pr_lo, &pr_hi);
-    hipStreamCreateWithPriority(&o->stream, hipStreamNonBlocking, pr_hi);
+    OP_TRY(o, "stream priority range",
+           hipDeviceGetStreamPriorityRange(&pr_lo, &pr_hi));
+    OP_TRY(o, "stream", o->own_stream(o->stream, hipStreamCreateWithPriority(
+                            &o->stream, hipStreamNonBlocking, pr_hi)));
     if (o->own_fstream) {
         /* ARROYO_AMD_FIRE_CUS=N confines both fire streams to the last N
          * CUs so update wavefronts own the rest (hard partition via CU
@@ -2425,20 +2337,22 @@ API void *arroyo_amd_create(const AmdWindowConfig *cfg) {
             uint32_t mask[8] = {};
             for (int b = 256 - fire_cus; b < 256; b++)
                 mask[b / 32] |= 1u << (b % 32);
-            hipExtStreamCreateWithCUMask(&o->fstream, 8, mask);
-            hipExtStreamCreateWithCUMask(&o->fstream2, 8, mask);
+            for (hipStream_t *fs : {&o->fstream, &o->fstream2})
+                OP_TRY(o, "fire stream",
+                       o->own_stream(*fs, hipExtStreamCreateWithCUMask(
+                                              fs, 8, mask)));
         } else {
-            hipStreamCreateWithPriority(&o->fstream, hipStreamNonBlocking,
-                                        pr_lo);
-            hipStreamCreateWithPriority(&o->fstream2, hipStreamNonBlocking,
-                                        pr_lo);
+            for (hipStream_t *fs : {&o->fstream, &o->fstream2})
+                OP_TRY(o, "fire stream",
+                       o->own_stream(*fs,
+                                     hipStreamCreateWithPriority(
+                                         fs, hipStreamNonBlocking, pr_lo)));
         }
-        hipEventCreateWithFlags(&o->ev_gate, hipEventDisableTiming);
-        hipEventCreateWithFlags(&o->ev_f1, hipEventDisableTiming);
-        hipEventCreateWithFlags(&o->ev_f2, hipEventDisableTiming);
-        hipEventCreateWithFlags(&o->ev_cpi, hipEventDisableTiming);
-        for (int i = 0; i < 4; i++)
-            hipEventCreateWithFlags(&o->ev_tail[i], hipEventDisableTiming);
+        for (hipEvent_t *ev : {&o->ev_gate, &o->ev_f1, &o->ev_f2, &o->ev_cpi,
+                               &o->ev_tail[0], &o->ev_tail[1], &o->ev_tail[2],
+                               &o->ev_tail[3]})
+            OP_TRY(o, "fire event",
+                   o->event_create(ev, hipEventDisableTiming));
     } else {
         o->fstream = o->stream;
         o->fstream2 = o->stream;
@@ -2448,11 +2362,12 @@ API void *arroyo_amd_create(const AmdWindowConfig *cfg) {
     o->fire_group = 0;
     o->spin = 1;
     if (const char *ev = getenv("ARROYO_AMD_SPIN")) o->spin = atoi(ev) != 0;
-    hipEventCreateWithFlags(&o->ev_sync, hipEventDisableTiming);
+    OP_TRY(o, "ev_sync", o->event_create(&o->ev_sync, hipEventDisableTiming));
     for (int i = 0; i < 2; i++) {
-        hipHostMalloc((void **)&o->h_epoch[i],
-                      (2 + (size_t)o->ring.R) * 8);
-        hipEventCreateWithFlags(&o->ev_epoch[i], hipEventDisableTiming);
+        OP_TRY(o, "h_epoch",
+               o->pinned_alloc(o->h_epoch[i], (2 + (size_t)o->ring.R) * 8));
+        OP_TRY(o, "ev_epoch",
+               o->event_create(&o->ev_epoch[i], hipEventDisableTiming));
     }
     o->epoch_head = o->epoch_cnt = 0;
     /* 2 groups of slack won the sweep (lag 1 throttles updates behind a
@@ -2468,25 +2383,16 @@ API void *arroyo_amd_create(const AmdWindowConfig *cfg) {
     o->retired_bin.assign(o->ring.R, EMPTY_TAG);
     /* pinned staging: 1M rows; enough columns for input batches and for
      * restore's raw-state batches */
-    o->stg.cap = 1 << 20;
-    o->stg.n = 0;
-    o->stg.ncols = o->n_in_cols > raw_cols - 1 ? o->n_in_cols : raw_cols - 1;
-    for (int i = 0; i < o->stg.ncols; i++) {
-        if (hipHostMalloc((void **)&o->stg.buf[i], (size_t)o->stg.cap * 8) !=
-                hipSuccess ||
-            hipMalloc((void **)&o->stg.dbuf[i], (size_t)o->stg.cap * 8) !=
-                hipSuccess) {
-            snprintf(g_err, sizeof g_err, "staging alloc failed");
-            delete o;
-            return nullptr;
-        }
-    }
+    OP_TRY_MSG(o, "staging alloc failed",
+               o->stg.alloc(o, o->n_in_cols > raw_cols - 1 ? o->n_in_cols
+                                                       : raw_cols - 1,
+                        1 << 20));
     o->host_out.resize(o->out_cols);
     return o;
 }
 
 API const char *arroyo_amd_last_error(void *h) {
-    return h ? ((GpuOp *)h)->err_msg : g_err;
+    return h ? ((GpuOp *)h)->err_msg : g_create_err;
 }
 
 /* 16 B vector loads need a row pair and 16 B-aligned ts/key columns */
@@ -2618,8 +2524,8 @@ static int launch_update(GpuOp *o, const int64_t *const *dcols, int64_t n_rows,
     if (sample && o->ev_pool.empty()) {
         o->ev_pool.resize(EV_POOL);
         for (auto &pr : o->ev_pool) {
-            hipEventCreate(&pr.first);
-            hipEventCreate(&pr.second);
+            HIP_CHECK(o, o->event_create(&pr.first));
+            HIP_CHECK(o, o->event_create(&pr.second));
         }
     }
     if (sample && o->ev_inflight.size() >= EV_POOL) harvest_events(o, 1);
@@ -2650,10 +2556,11 @@ static int launch_update(GpuOp *o, const int64_t *const *dcols, int64_t n_rows,
 /* normalize a batch's composite keys to dictionary ids (device cols) */
 static int mk_encode(GpuOp *o, const int64_t *const *kcols, int64_t n_rows) {
     if (n_rows > o->keyid_in_cap) {
-        hipFree(o->d_keyid_in);
+        o->release(o->d_keyid_in);
+        o->keyid_in_cap = 0;
+        HIP_CHECK(o, o->dev_alloc(o->d_keyid_in,
+                                  (size_t)(n_rows + (n_rows >> 2)) * 8));
         o->keyid_in_cap = n_rows + (n_rows >> 2);
-        HIP_CHECK(o, hipMalloc((void **)&o->d_keyid_in,
-                               (size_t)o->keyid_in_cap * 8));
     }
     DictEncArgs E = {};
     for (int k = 0; k < o->cfg.n_keys; k++) E.kcols[k] = kcols[k];
@@ -2687,20 +2594,15 @@ static int mk_engine_cols(GpuOp *o, const int64_t *const *dcols,
 
 static int flush_staged(GpuOp *o) {
     if (o->stg.n == 0) return 0;
-    for (int i = 0; i < o->n_in_cols; i++)
-        HIP_CHECK(o, hipMemcpyAsync(o->stg.dbuf[i], o->stg.buf[i],
-                                    (size_t)o->stg.n * 8,
-                                    hipMemcpyHostToDevice, o->stream));
-    const int64_t *dcols[6];
+    /* up to 4 key + 4 value columns + ts; the engine view below has one key */
+    const int64_t *dcols[OP_STG_MAX_COLS];
+    if (o->stg.upload(o, o->n_in_cols, o->stg.n, dcols)) return 1;
     int rc;
     if (o->mk) {
         const int64_t *eng[6];
-        if (mk_engine_cols(o, (const int64_t *const *)o->stg.dbuf, o->stg.n,
-                           eng))
-            return 1;
+        if (mk_engine_cols(o, dcols, o->stg.n, eng)) return 1;
         rc = launch_update(o, eng, o->stg.n, 0);
     } else {
-        for (int i = 0; i < o->n_in_cols; i++) dcols[i] = o->stg.dbuf[i];
         rc = launch_update(o, dcols, o->stg.n, 0);
     }
     o->stg.n = 0;
@@ -2720,7 +2622,7 @@ API int arroyo_amd_process_batch(void *h, const int64_t *const *cols,
         int64_t take = n_rows - done;
         if (take > o->stg.cap - o->stg.n) take = o->stg.cap - o->stg.n;
         for (int i = 0; i < n_cols; i++)
-            memcpy(o->stg.buf[i] + o->stg.n, cols[i] + done, (size_t)take * 8);
+            memcpy(o->stg.h[i] + o->stg.n, cols[i] + done, (size_t)take * 8);
         o->stg.n += take;
         done += take;
         if (o->stg.n == o->stg.cap)
@@ -3305,7 +3207,6 @@ static int advance(GpuOp *o) {
 }
 
 static int build_out(GpuOp *o, AmdOutBatch *out, int raw_states) {
-    memset(out, 0, sizeof *out);
     int ncols = o->out_cols;
     if (raw_states) {
         ncols = o->cfg.n_keys + 1;
@@ -3313,16 +3214,10 @@ static int build_out(GpuOp *o, AmdOutBatch *out, int raw_states) {
             ncols += (o->agg.op[a] == AMD_AGG_AVG) ? 2 : 1;
     }
     int64_t n = o->host_out.empty() ? 0 : (int64_t)o->host_out[0].size();
-    out->n_rows = n;
-    out->n_cols = ncols;
-    out->cols = (void **)calloc(ncols, sizeof(void *));
-    out->is_f64 = (int32_t *)calloc(ncols, sizeof(int32_t));
-    if (!out->cols || !out->is_f64) goto oom;
-    for (int i = 0; i < ncols; i++) {
-        out->cols[i] = malloc((size_t)(n ? n : 1) * 8);
-        if (!out->cols[i]) goto oom;
-        if (n) memcpy(out->cols[i], o->host_out[i].data(), (size_t)n * 8);
-    }
+    /* loud error per the library convention, never a null-deref */
+    if (op_out_alloc(o, out, n, ncols, "build_out")) return 1;
+    for (int i = 0; n && i < ncols; i++)
+        memcpy(out->cols[i], o->host_out[i].data(), (size_t)n * 8);
     if (!raw_states) {
         for (int a = 0; a < o->agg.n_aggs; a++)
             if (o->agg.op[a] == AMD_AGG_AVG || o->agg.isf[a])
@@ -3341,15 +3236,6 @@ static int build_out(GpuOp *o, AmdOutBatch *out, int raw_states) {
     }
     for (auto &v : o->host_out) v.clear();
     return 0;
-oom:
-    /* loud error per the library convention, never a null-deref */
-    if (out->cols)
-        for (int i = 0; i < ncols; i++) free(out->cols[i]);
-    free(out->cols);
-    free(out->is_f64);
-    memset(out, 0, sizeof *out);
-    snprintf(o->err_msg, sizeof o->err_msg, "build_out: host allocation failed");
-    return 1;
 }
 
 /* per-watermark firing logic, after the (shared) device status fold */
@@ -3626,8 +3512,8 @@ API int arroyo_amd_restore(void *h, const int64_t *const *cols,
         int sc = 0;
         for (int c = 0; c < n_cols - 1; c++) {
             for (int64_t i = 0; i < n; i++)
-                o->stg.buf[sc][i] = cols[c][kv.second[i]];
-            HIP_CHECK(o, hipMemcpyAsync(o->stg.dbuf[sc], o->stg.buf[sc],
+                o->stg.h[sc][i] = cols[c][kv.second[i]];
+            HIP_CHECK(o, hipMemcpyAsync(o->stg.d[sc], o->stg.h[sc],
                                         (size_t)n * 8, hipMemcpyHostToDevice,
                                         o->stream));
             sc++;
@@ -3635,14 +3521,14 @@ API int arroyo_amd_restore(void *h, const int64_t *const *cols,
         RestoreArgs R = {};
         int c2 = 0;
         if (o->mk) {
-            if (mk_encode(o, (const int64_t *const *)o->stg.dbuf, n))
+            if (mk_encode(o, (const int64_t *const *)o->stg.d, n))
                 return 1;
             R.key_col = o->d_keyid_in;
             c2 = o->cfg.n_keys;
         } else {
-            R.key_col = o->cfg.n_keys ? o->stg.dbuf[c2++] : nullptr;
+            R.key_col = o->cfg.n_keys ? o->stg.d[c2++] : nullptr;
         }
-        for (int s = 0; s < swords_total; s++) R.scols[s] = o->stg.dbuf[c2++];
+        for (int s = 0; s < swords_total; s++) R.scols[s] = o->stg.d[c2++];
         memcpy(R.swords, swords, sizeof swords);
         R.n_rows = n;
         R.pane = p;
@@ -3683,71 +3569,18 @@ API int arroyo_amd_restore(void *h, const int64_t *const *cols,
 
 API void arroyo_amd_free_out(AmdOutBatch *out) {
     if (!out) return;
-    for (int i = 0; i < out->n_cols; i++) {
-        if (out->on_device)
-            hipFree(out->cols[i]);   /* device-resident emission (ABI doc) */
-        else
-            free(out->cols[i]);
-    }
-    if (out->validity) {
-        for (int i = 0; i < out->n_cols; i++) free(out->validity[i]);
-        free(out->validity);
-    }
-    free(out->cols);
-    free(out->is_f64);
-    memset(out, 0, sizeof *out);
+    if (out->on_device)   /* device-resident emission (ABI doc) */
+        for (int i = 0; out->cols && i < out->n_cols; i++) {
+            (void)hipFree(out->cols[i]);
+            out->cols[i] = nullptr;
+        }
+    out_free_host(out);
 }
 
 API void arroyo_amd_destroy(void *h) {
     GpuOp *o = (GpuOp *)h;
     if (!o) return;
-    hipStreamSynchronize(o->stream);
-    if (o->fstream != o->stream) hipStreamSynchronize(o->fstream);
-    harvest_events(o, 1);
-    hipEventDestroy(o->ev_sync);
-    for (int i = 0; i < 2; i++) {
-        hipHostFree(o->h_epoch[i]);
-        hipEventDestroy(o->ev_epoch[i]);
-    }
-    if (o->fstream != o->stream) {
-        hipStreamSynchronize(o->fstream2);
-        hipEventDestroy(o->ev_gate);
-        hipEventDestroy(o->ev_f1);
-        hipEventDestroy(o->ev_f2);
-        hipEventDestroy(o->ev_cpi);
-        for (int i = 0; i < 4; i++) hipEventDestroy(o->ev_tail[i]);
-        hipStreamDestroy(o->fstream);
-        hipStreamDestroy(o->fstream2);
-    }
-    for (int i = 0; i < o->n_out_alloc; i++) hipFree(o->d_out2[i]);
-    for (auto &pr : o->ev_pool) {
-        hipEventDestroy(pr.first);
-        hipEventDestroy(pr.second);
-    }
-    hipFree(o->ring.keys);
-    hipFree(o->ring.state);
-    hipFree(o->d_status);
-    hipHostFree(o->h_status);
-    hipFree(o->ring.spec_used);
-    hipFree(o->ring.spec_state);
-    hipFree(o->m_keys);
-    hipFree(o->m_zero_blob);
-    for (int i = 0; i < o->n_out_alloc; i++) hipFree(o->d_out[i]);
-    hipFree(o->d_emitted);
-    hipFree(o->d_fire_cur);
-    hipFree(o->d_fire_cur2);
-    hipFree(o->cpi_entries);
-    hipFree(o->cpi_cnt);
-    hipFree(o->d_dict_digest);
-    hipFree(o->d_dict_keys);
-    hipFree(o->d_dict_ready);
-    hipFree(o->d_keyid_in);
-    hipFree(o->d_keyid_out);
-    for (int i = 0; i < o->stg.ncols; i++) {
-        hipHostFree(o->stg.buf[i]);
-        hipFree(o->stg.dbuf[i]);
-    }
-    hipStreamDestroy(o->stream);
+    harvest_events(o, 1);   /* waits for every sampled launch */
     delete o;
 }
 

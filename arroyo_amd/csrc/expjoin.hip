@@ -31,32 +31,16 @@
  * the reference's updating_inner_join golden vector) by
  * tests/test_expjoin.py.
  */
-#include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-#include "../../include/arroyo_amd_types.h"
-
-#define API extern "C" __attribute__((visibility("default")))
+#include "op_common.h"
 
 namespace ejoin {
 
-#define EMPTY_KEY (-1LL)
 #define EJERR_TABLE_FULL 1
 #define EJERR_POOL_FULL  2
 #define EJERR_OUT_CAP    3
 #define EJERR_RETRACT    4
-
-__device__ inline uint64_t hash64(uint64_t x) {
-    x += 0x9e3779b97f4a7c15ULL;
-    x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ULL;
-    x = (x ^ (x >> 27)) * 0x94d049bb133111ebULL;
-    return x ^ (x >> 31);
-}
 
 /* one side's device state */
 struct SideMap {
@@ -462,9 +446,7 @@ k_ej_upd(EjUpdArgs U) {
 
 using namespace ejoin;
 
-static char g_ej_err[256];
-
-struct GpuExpJoin {
+struct GpuExpJoin : OpBase {
     AmdExpJoinConfig cfg;
     SideMap side[2];
     /* updating/outer-mode scratch: per-batch (slot<<32|row) sort + key
@@ -476,65 +458,42 @@ struct GpuExpJoin {
     size_t ejtmp_bytes = 0;
     int64_t *d_out[16];
     unsigned long long *d_n_out;
-    int *d_err;
-    int64_t *stg_h[12], *stg_d[12];
-    int64_t stg_cap;
+    Staging stg;
     int out_cols;
     int64_t out_cap;
     int has_wm; uint64_t wm;
-    hipStream_t stream;
-    char err_msg[512];
 };
 
-#define EJHIP(o, call)                                                        \
-    do {                                                                      \
-        hipError_t _e = (call);                                               \
-        if (_e != hipSuccess) {                                               \
-            snprintf((o)->err_msg, sizeof (o)->err_msg, "%s:%d hip: %s",      \
-                     __FILE__, __LINE__, hipGetErrorString(_e));              \
-            return 1;                                                         \
-        }                                                                     \
-    } while (0)
+/* everything of a side but its key table: what expire() rebuilds */
+static hipError_t ej_alloc_chains(GpuExpJoin *o, SideMap *S) {
+    size_t C1 = (size_t)S->C + 1, R = (size_t)S->R;
+    hipError_t e = o->dev_alloc(S->head, C1 * 4, 0xFF);
+    if (!e) e = o->dev_alloc(S->next, R * 4);
+    if (!e) e = o->dev_alloc(S->vals, (size_t)(S->nv ? S->nv : 1) * R * 8);
+    if (!e) e = o->dev_alloc(S->ts, R * 8);
+    if (!e) e = o->dev_alloc(S->cnt, C1 * 4, 0);
+    if (!e) e = o->dev_alloc(S->cursor, 8, 0);
+    return e;
+}
 
-static int ej_alloc_side(GpuExpJoin *o, SideMap *S, uint32_t C, int64_t R,
-                         int32_t nv) {
+static hipError_t ej_alloc_side(GpuExpJoin *o, SideMap *S, uint32_t C,
+                                int64_t R, int32_t nv) {
     S->C = C;
     S->R = R;
     S->nv = nv;
-    EJHIP(o, hipMalloc((void **)&S->keys, (size_t)C * 8));
-    EJHIP(o, hipMalloc((void **)&S->head, ((size_t)C + 1) * 4));
-    EJHIP(o, hipMalloc((void **)&S->next, (size_t)R * 4));
-    EJHIP(o, hipMalloc((void **)&S->vals,
-                       (size_t)(nv ? nv : 1) * (size_t)R * 8));
-    EJHIP(o, hipMalloc((void **)&S->ts, (size_t)R * 8));
-    EJHIP(o, hipMalloc((void **)&S->cnt, ((size_t)C + 1) * 4));
-    EJHIP(o, hipMalloc((void **)&S->cursor, 8));
-    EJHIP(o, hipMemset(S->keys, 0xFF, (size_t)C * 8));
-    EJHIP(o, hipMemset(S->head, 0xFF, ((size_t)C + 1) * 4));
-    EJHIP(o, hipMemset(S->cnt, 0, ((size_t)C + 1) * 4));
-    EJHIP(o, hipMemset(S->cursor, 0, 8));
-    return 0;
-}
-
-static void ej_free_side(SideMap *S) {
-    hipFree(S->keys);
-    hipFree(S->head);
-    hipFree(S->next);
-    hipFree(S->vals);
-    hipFree(S->ts);
-    hipFree(S->cnt);
-    hipFree(S->cursor);
+    hipError_t e = o->dev_alloc(S->keys, (size_t)C * 8, 0xFF);
+    return e ? e : ej_alloc_chains(o, S);
 }
 
 API void *arroyo_amd_expjoin_create(const AmdExpJoinConfig *cfg) {
     if (!cfg || cfg->n_keys != 1 || cfg->n_left_vals < 0 ||
         cfg->n_left_vals > 8 || cfg->n_right_vals < 0 ||
         cfg->n_right_vals > 8 || cfg->ttl_nanos == 0) {
-        snprintf(g_ej_err, sizeof g_ej_err, "invalid expjoin config");
+        snprintf(g_create_err, sizeof g_create_err, "invalid expjoin config");
         return nullptr;
     }
     if (cfg->join_type < 0 || cfg->join_type > AMD_JOIN_FULL) {
-        snprintf(g_ej_err, sizeof g_ej_err, "invalid join_type");
+        snprintf(g_create_err, sizeof g_create_err, "invalid join_type");
         return nullptr;
     }
     GpuExpJoin *o = new GpuExpJoin();
@@ -546,7 +505,7 @@ API void *arroyo_amd_expjoin_create(const AmdExpJoinConfig *cfg) {
                   (cfg->join_type != AMD_JOIN_INNER || cfg->updating ? 1 : 0);
     o->out_cap = 1ll << (cfg->log2_out_cap ? cfg->log2_out_cap : 20);
     if (hipSetDevice(cfg->device) != hipSuccess) {
-        snprintf(g_ej_err, sizeof g_ej_err,
+        snprintf(g_create_err, sizeof g_create_err,
                  "hipSetDevice(%d) failed: no HIP device (no CPU fallback)",
                  cfg->device);
         delete o;
@@ -555,97 +514,65 @@ API void *arroyo_amd_expjoin_create(const AmdExpJoinConfig *cfg) {
     uint32_t C = 1u << (cfg->log2_capacity ? cfg->log2_capacity : 16);
     int64_t R = 1ll << (cfg->log2_rows_cap ? cfg->log2_rows_cap : 20);
     for (int s = 0; s < 2; s++)
-        if (ej_alloc_side(o, &o->side[s], C, R,
-                          s == 0 ? cfg->n_left_vals : cfg->n_right_vals)) {
-            snprintf(g_ej_err, sizeof g_ej_err, "%s", o->err_msg);
-            delete o;
-            return nullptr;
-        }
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < o->out_cols && e == hipSuccess; i++)
-        e = hipMalloc((void **)&o->d_out[i], (size_t)o->out_cap * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&o->d_n_out, 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&o->d_err, 4);
-    if (e != hipSuccess) {
-        snprintf(g_ej_err, sizeof g_ej_err, "expjoin alloc: %s",
-                 hipGetErrorString(e));
-        delete o;
-        return nullptr;
-    }
-    hipMemset(o->d_err, 0, 4);
+        OP_TRY(o, "expjoin alloc",
+               ej_alloc_side(o, &o->side[s], C, R,
+                             s == 0 ? cfg->n_left_vals : cfg->n_right_vals));
+    for (int i = 0; i < o->out_cols; i++)
+        OP_TRY(o, "expjoin alloc",
+               o->dev_alloc(o->d_out[i], (size_t)o->out_cap * 8));
     /* the device-resident ingest path accumulates matches from a cursor
      * that must start at zero (the host path resets it per batch, which
      * masked a reused allocation's stale value here) */
-    hipMemset(o->d_n_out, 0, 8);
-    hipStreamCreate(&o->stream);
-    o->stg_cap = 1 << 20;
+    OP_TRY(o, "expjoin alloc", o->dev_alloc(o->d_n_out, 8, 0));
+    OP_TRY(o, "expjoin alloc", o->dev_alloc(o->d_err, 4, 0));
+    OP_TRY(o, "hipStreamCreate", o->stream_create(&o->stream));
     int max_in = 1 + (cfg->n_left_vals > cfg->n_right_vals
                           ? cfg->n_left_vals
                           : cfg->n_right_vals) +
                  (cfg->updating ? 1 : 0) + 1;
-    for (int c = 0; c < max_in; c++) {
-        if (hipHostMalloc((void **)&o->stg_h[c], (size_t)o->stg_cap * 8) !=
-                hipSuccess ||
-            hipMalloc((void **)&o->stg_d[c], (size_t)o->stg_cap * 8) !=
-                hipSuccess) {
-            snprintf(g_ej_err, sizeof g_ej_err,
-                     "expjoin staging alloc failed");
-            delete o;
-            return nullptr;
-        }
-    }
+    OP_TRY_MSG(o, "expjoin staging alloc failed",
+               o->stg.alloc(o, max_in, 1 << 20));
     return o;
 }
 
 API const char *arroyo_amd_expjoin_last_error(void *h) {
-    return h ? ((GpuExpJoin *)h)->err_msg : g_ej_err;
+    return h ? ((GpuExpJoin *)h)->err_msg : g_create_err;
 }
 
 /* Arrow validity bitmaps for the updating/outer output's null-padded
  * value columns ([key, lvals, rvals, ts, lp, rp, retract]) */
-static void ej_fill_validity(GpuExpJoin *o, AmdOutBatch *out) {
-    if (o->cfg.join_type == AMD_JOIN_INNER) return;
+static int ej_fill_validity(GpuExpJoin *o, AmdOutBatch *out) {
+    if (o->cfg.join_type == AMD_JOIN_INNER) return 0;
     int nlv = o->cfg.n_left_vals, nrv = o->cfg.n_right_vals;
     int lp = 1 + nlv + nrv + 1;
     int64_t n = out->n_rows;
-    out->validity = (uint8_t **)calloc(out->n_cols, sizeof(uint8_t *));
-    if (!out->validity || n == 0) return;
-    size_t nbytes = (size_t)((n + 7) / 8);
-    for (int g = 0; g < 2; g++) {
+    bool oom = out_alloc_validity(out);
+    for (int g = 0; n && !oom && g < 2; g++) {
         int base = g == 0 ? 1 : 1 + nlv;
         int cnt = g == 0 ? nlv : nrv;
         const int64_t *pres = (const int64_t *)out->cols[g == 0 ? lp
                                                                 : lp + 1];
-        for (int c = base; c < base + cnt; c++) {
-            uint8_t *bm = (uint8_t *)calloc(nbytes, 1);
-            if (!bm) continue;
+        for (int c = base; c < base + cnt && !oom; c++) {
+            uint8_t *bm = out_validity_col(out, c);
+            if (!bm) { oom = true; break; }
             for (int64_t r = 0; r < n; r++)
                 if (pres[r]) bm[r >> 3] |= (uint8_t)(1u << (r & 7));
-            out->validity[c] = bm;
         }
     }
-}
-
-static int ej_check_err(GpuExpJoin *o) {
-    int e = 0;
-    EJHIP(o, hipMemcpyAsync(&e, o->d_err, 4, hipMemcpyDeviceToHost,
-                            o->stream));
-    EJHIP(o, hipStreamSynchronize(o->stream));
-    if (!e) return 0;
-    const char *msg =
-        e == EJERR_TABLE_FULL ? "join key table full; raise log2_capacity"
-        : e == EJERR_POOL_FULL
-            ? "stored-row pool full; raise log2_rows_cap or expire()"
-        : e == EJERR_OUT_CAP ? "output buffer full; raise log2_out_cap"
-        : e == EJERR_RETRACT ? "retract of unknown row"
-                             : "device error";
-    snprintf(o->err_msg, sizeof o->err_msg, "%s", msg);
+    if (!oom) return 0;
+    out_free_host(out);
+    snprintf(o->err_msg, sizeof o->err_msg,
+             "validity bitmap allocation failed");
     return 1;
 }
 
-static int ej_grid(int64_t want_threads) {
-    int64_t want = (want_threads + 255) / 256;
-    return (int)(want > 4096 ? 4096 : (want < 1 ? 1 : want));
+static const char *ej_err_msg(int e) {
+    return e == EJERR_TABLE_FULL ? "join key table full; raise log2_capacity"
+           : e == EJERR_POOL_FULL
+               ? "stored-row pool full; raise log2_rows_cap or expire()"
+           : e == EJERR_OUT_CAP ? "output buffer full; raise log2_out_cap"
+           : e == EJERR_RETRACT ? "retract of unknown row"
+                                : "device error";
 }
 
 /* updating/outer ingest: group the batch by key, then replay each key's
@@ -654,29 +581,30 @@ static int ej_ingest_upd(GpuExpJoin *o, int32_t side,
                          const int64_t *const *dcols, int64_t n_rows) {
     int32_t nv = side == 0 ? o->cfg.n_left_vals : o->cfg.n_right_vals;
     if (!o->d_sortin) {
-        EJHIP(o, hipMalloc((void **)&o->d_sortin, (size_t)o->stg_cap * 8));
-        EJHIP(o, hipMalloc((void **)&o->d_sortout, (size_t)o->stg_cap * 8));
-        EJHIP(o, hipMalloc((void **)&o->d_segs, (size_t)o->stg_cap * 4));
-        EJHIP(o, hipMalloc((void **)&o->d_nseg, 4));
+        HIP_CHECK(o, o->dev_alloc(o->d_sortin, (size_t)o->stg.cap * 8));
+        HIP_CHECK(o, o->dev_alloc(o->d_sortout, (size_t)o->stg.cap * 8));
+        HIP_CHECK(o, o->dev_alloc(o->d_segs, (size_t)o->stg.cap * 4));
+        HIP_CHECK(o, o->dev_alloc(o->d_nseg, 4));
         o->ejtmp_bytes = 0;
-        hipcub::DeviceRadixSort::SortKeys(nullptr, o->ejtmp_bytes,
-                                          o->d_sortin, o->d_sortout,
-                                          (int)o->stg_cap);
-        EJHIP(o, hipMalloc(&o->d_ejtmp, o->ejtmp_bytes ? o->ejtmp_bytes : 1));
+        HIP_CHECK(o, hipcub::DeviceRadixSort::SortKeys(
+                         nullptr, o->ejtmp_bytes, o->d_sortin, o->d_sortout,
+                         (int)o->stg.cap));
+        HIP_CHECK(o, o->dev_alloc(o->d_ejtmp,
+                                  o->ejtmp_bytes ? o->ejtmp_bytes : 1));
     }
-    hipLaunchKernelGGL(k_ej_slots, dim3(ej_grid(n_rows)), dim3(256), 0,
+    hipLaunchKernelGGL(k_ej_slots, dim3(grid_for(n_rows, 4096)), dim3(256), 0,
                        o->stream, dcols[0], n_rows, o->side[side],
                        o->d_sortin, o->d_err);
-    EJHIP(o, hipGetLastError());
+    HIP_CHECK(o, hipGetLastError());
     size_t tmp = o->ejtmp_bytes;
-    hipcub::DeviceRadixSort::SortKeys(o->d_ejtmp, tmp, o->d_sortin,
-                                      o->d_sortout, (int)n_rows, 0, 64,
-                                      o->stream);
-    EJHIP(o, hipMemsetAsync(o->d_nseg, 0, 4, o->stream));
-    hipLaunchKernelGGL(k_ej_segs, dim3(ej_grid(n_rows)), dim3(256), 0,
+    HIP_CHECK(o, hipcub::DeviceRadixSort::SortKeys(
+                     o->d_ejtmp, tmp, o->d_sortin, o->d_sortout, (int)n_rows,
+                     0, 64, o->stream));
+    HIP_CHECK(o, hipMemsetAsync(o->d_nseg, 0, 4, o->stream));
+    hipLaunchKernelGGL(k_ej_segs, dim3(grid_for(n_rows, 4096)), dim3(256), 0,
                        o->stream, o->d_sortout, n_rows, o->d_segs,
                        o->d_nseg);
-    EJHIP(o, hipGetLastError());
+    HIP_CHECK(o, hipGetLastError());
     EjUpdArgs U = {};
     for (int c = 0; c < 1 + nv + (o->cfg.updating ? 1 : 0) + 1; c++)
         U.cols[c] = dcols[c];
@@ -696,9 +624,9 @@ static int ej_ingest_upd(GpuExpJoin *o, int32_t side,
     U.n_out = o->d_n_out;
     U.out_cap = o->out_cap;
     U.err = o->d_err;
-    hipLaunchKernelGGL(k_ej_upd, dim3(ej_grid(n_rows)), dim3(256), 0,
+    hipLaunchKernelGGL(k_ej_upd, dim3(grid_for(n_rows, 4096)), dim3(256), 0,
                        o->stream, U);
-    EJHIP(o, hipGetLastError());
+    HIP_CHECK(o, hipGetLastError());
     return 0;
 }
 
@@ -718,9 +646,10 @@ static int ej_ingest(GpuExpJoin *o, int32_t side, const int64_t *const *dcols,
         P.n_out = o->d_n_out;
         P.out_cap = o->out_cap;
         P.err = o->d_err;
-        hipLaunchKernelGGL(k_ej_probe, dim3(ej_grid(n_rows)), dim3(256), 0,
+        hipLaunchKernelGGL(k_ej_probe, dim3(grid_for(n_rows, 4096)),
+                           dim3(256), 0,
                            o->stream, P);
-        EJHIP(o, hipGetLastError());
+        HIP_CHECK(o, hipGetLastError());
     }
     InsertArgs I = {};
     for (int c = 0; c < 1 + nv + 1; c++) I.cols[c] = dcols[c];
@@ -728,9 +657,9 @@ static int ej_ingest(GpuExpJoin *o, int32_t side, const int64_t *const *dcols,
     I.n_rows = n_rows;
     I.own = o->side[side];
     I.err = o->d_err;
-    hipLaunchKernelGGL(k_ej_insert, dim3(ej_grid(n_rows)), dim3(256), 0,
+    hipLaunchKernelGGL(k_ej_insert, dim3(grid_for(n_rows, 4096)), dim3(256), 0,
                        o->stream, I);
-    EJHIP(o, hipGetLastError());
+    HIP_CHECK(o, hipGetLastError());
     return 0;
 }
 
@@ -740,7 +669,7 @@ static int ej_copy_in(GpuExpJoin *o, int32_t side,
     int64_t done = 0;
     while (done < n_rows) {
         int64_t take = n_rows - done;
-        if (take > o->stg_cap) take = o->stg_cap;
+        if (take > o->stg.cap) take = o->stg.cap;
         const int64_t *dcols[12];
         if (cutoff) {
             /* restore-time TTL filter: keep ts >= cutoff */
@@ -749,30 +678,27 @@ static int ej_copy_in(GpuExpJoin *o, int32_t side,
             for (int64_t i = 0; i < take; i++) {
                 if ((uint64_t)ts[done + i] < cutoff) continue;
                 for (int c = 0; c < n_cols; c++)
-                    o->stg_h[c][w] = cols[c][done + i];
+                    o->stg.h[c][w] = cols[c][done + i];
                 w++;
             }
-            for (int c = 0; c < n_cols; c++) {
-                EJHIP(o, hipMemcpyAsync(o->stg_d[c], o->stg_h[c],
-                                        (size_t)(w ? w : 1) * 8,
-                                        hipMemcpyHostToDevice, o->stream));
-                dcols[c] = o->stg_d[c];
-            }
-            if (w && ej_ingest(o, side, dcols, w, emit)) return 1;
-        } else {
-            for (int c = 0; c < n_cols; c++) {
-                memcpy(o->stg_h[c], cols[c] + done, (size_t)take * 8);
-                EJHIP(o, hipMemcpyAsync(o->stg_d[c], o->stg_h[c],
-                                        (size_t)take * 8,
-                                        hipMemcpyHostToDevice, o->stream));
-                dcols[c] = o->stg_d[c];
-            }
-            if (ej_ingest(o, side, dcols, take, emit)) return 1;
+            if (w && (o->stg.upload(o, n_cols, w, dcols) ||
+                      ej_ingest(o, side, dcols, w, emit)))
+                return 1;
+        } else if (o->stg.stage_chunk(o, cols, n_cols, done, take, dcols) ||
+                   ej_ingest(o, side, dcols, take, emit)) {
+            return 1;
         }
-        EJHIP(o, hipStreamSynchronize(o->stream));
+        HIP_CHECK(o, hipStreamSynchronize(o->stream));
         done += take;
     }
     return 0;
+}
+
+/* the first n rows of d_out as a host batch, with the outer-join bitmaps */
+static int ej_out(GpuExpJoin *o, AmdOutBatch *out, int64_t n, int n_cols,
+                  const char *who) {
+    return op_out_alloc(o, out, n, n_cols, who) ||
+           out_copy_cols(o, out, o->d_out, n) || ej_fill_validity(o, out);
 }
 
 API int arroyo_amd_expjoin_process_batch(void *h, int32_t side,
@@ -787,29 +713,14 @@ API int arroyo_amd_expjoin_process_batch(void *h, int32_t side,
                  side, want);
         return 1;
     }
-    EJHIP(o, hipMemsetAsync(o->d_n_out, 0, 8, o->stream));
+    HIP_CHECK(o, hipMemsetAsync(o->d_n_out, 0, 8, o->stream));
     if (ej_copy_in(o, side, cols, n_cols, n_rows, 1, 0)) return 1;
     unsigned long long n = 0;
-    EJHIP(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
-                            o->stream));
-    EJHIP(o, hipStreamSynchronize(o->stream));
-    if (ej_check_err(o)) return 1;
-    if (out) {
-        memset(out, 0, sizeof *out);
-        out->n_rows = (int64_t)n;
-        out->n_cols = o->out_cols;
-        out->cols = (void **)calloc(o->out_cols, sizeof(void *));
-        out->is_f64 = (int32_t *)calloc(o->out_cols, sizeof(int32_t));
-        for (int i = 0; i < o->out_cols; i++) {
-            out->cols[i] = malloc((size_t)(n ? n : 1) * 8);
-            if (n)
-                EJHIP(o, hipMemcpyAsync(out->cols[i], o->d_out[i],
-                                        (size_t)n * 8, hipMemcpyDeviceToHost,
-                                        o->stream));
-        }
-        EJHIP(o, hipStreamSynchronize(o->stream));
-        ej_fill_validity(o, out);
-    }
+    HIP_CHECK(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
+                                o->stream));
+    HIP_CHECK(o, hipStreamSynchronize(o->stream));
+    if (op_check_err(o, ej_err_msg)) return 1;
+    if (out && ej_out(o, out, (int64_t)n, o->out_cols, __func__)) return 1;
     return 0;
 }
 
@@ -835,24 +746,12 @@ API int arroyo_amd_expjoin_process_batch_device(void *h, int32_t side,
 API int arroyo_amd_expjoin_collect(void *h, AmdOutBatch *out) {
     GpuExpJoin *o = (GpuExpJoin *)h;
     unsigned long long n = 0;
-    EJHIP(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
-                            o->stream));
-    EJHIP(o, hipStreamSynchronize(o->stream));
-    if (ej_check_err(o)) return 1;
-    memset(out, 0, sizeof *out);
-    out->n_rows = (int64_t)n;
-    out->n_cols = o->out_cols;
-    out->cols = (void **)calloc(o->out_cols, sizeof(void *));
-    out->is_f64 = (int32_t *)calloc(o->out_cols, sizeof(int32_t));
-    for (int i = 0; i < o->out_cols; i++) {
-        out->cols[i] = malloc((size_t)(n ? n : 1) * 8);
-        if (n)
-            EJHIP(o, hipMemcpyAsync(out->cols[i], o->d_out[i], (size_t)n * 8,
-                                    hipMemcpyDeviceToHost, o->stream));
-    }
-    EJHIP(o, hipStreamSynchronize(o->stream));
-    ej_fill_validity(o, out);
-    EJHIP(o, hipMemsetAsync(o->d_n_out, 0, 8, o->stream));
+    HIP_CHECK(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
+                                o->stream));
+    HIP_CHECK(o, hipStreamSynchronize(o->stream));
+    if (op_check_err(o, ej_err_msg)) return 1;
+    if (ej_out(o, out, (int64_t)n, o->out_cols, __func__)) return 1;
+    HIP_CHECK(o, hipMemsetAsync(o->d_n_out, 0, 8, o->stream));
     return 0;
 }
 
@@ -863,12 +762,12 @@ API int arroyo_amd_expjoin_collect(void *h, AmdOutBatch *out) {
 API int arroyo_amd_expjoin_match_count(void *h, int64_t *n_matches) {
     GpuExpJoin *o = (GpuExpJoin *)h;
     unsigned long long n = 0;
-    EJHIP(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
-                            o->stream));
-    EJHIP(o, hipStreamSynchronize(o->stream));
-    if (ej_check_err(o)) return 1;
+    HIP_CHECK(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
+                                o->stream));
+    HIP_CHECK(o, hipStreamSynchronize(o->stream));
+    if (op_check_err(o, ej_err_msg)) return 1;
     *n_matches = (int64_t)n;
-    EJHIP(o, hipMemsetAsync(o->d_n_out, 0, 8, o->stream));
+    HIP_CHECK(o, hipMemsetAsync(o->d_n_out, 0, 8, o->stream));
     return 0;
 }
 
@@ -876,7 +775,7 @@ API int arroyo_amd_expjoin_handle_watermark(void *h, uint64_t wm) {
     GpuExpJoin *o = (GpuExpJoin *)h;
     o->has_wm = 1;
     o->wm = wm;
-    return ej_check_err(o);
+    return op_check_err(o, ej_err_msg);
 }
 
 API int arroyo_amd_expjoin_expire(void *h) {
@@ -884,83 +783,53 @@ API int arroyo_amd_expjoin_expire(void *h) {
     if (!o->has_wm || o->wm < o->cfg.ttl_nanos) return 0;
     uint64_t cutoff = o->wm - o->cfg.ttl_nanos;
     for (int s = 0; s < 2; s++) {
-        SideMap fresh = {};
         SideMap *S = &o->side[s];
-        fresh.keys = S->keys;  /* key table survives; chains rebuilt */
-        fresh.C = S->C;
-        fresh.R = S->R;
-        fresh.nv = S->nv;
-        EJHIP(o, hipMalloc((void **)&fresh.head, ((size_t)S->C + 1) * 4));
-        EJHIP(o, hipMalloc((void **)&fresh.next, (size_t)S->R * 4));
-        EJHIP(o, hipMalloc((void **)&fresh.vals,
-                           (size_t)(S->nv ? S->nv : 1) * (size_t)S->R * 8));
-        EJHIP(o, hipMalloc((void **)&fresh.ts, (size_t)S->R * 8));
-        EJHIP(o, hipMalloc((void **)&fresh.cnt, ((size_t)S->C + 1) * 4));
-        EJHIP(o, hipMalloc((void **)&fresh.cursor, 8));
-        EJHIP(o, hipMemsetAsync(fresh.head, 0xFF, ((size_t)S->C + 1) * 4,
-                                o->stream));
-        EJHIP(o, hipMemsetAsync(fresh.cnt, 0, ((size_t)S->C + 1) * 4,
-                                o->stream));
-        EJHIP(o, hipMemsetAsync(fresh.cursor, 0, 8, o->stream));
+        SideMap fresh = *S;  /* key table survives; chains rebuilt */
+        HIP_CHECK(o, ej_alloc_chains(o, &fresh));
         CompactArgs A = {};
         A.src = *S;
         A.dst = fresh;
         A.cutoff = cutoff;
         A.err = o->d_err;
-        hipLaunchKernelGGL(k_ej_compact, dim3(ej_grid((int64_t)S->C + 1)),
+        hipLaunchKernelGGL(k_ej_compact,
+                           dim3(grid_for((int64_t)S->C + 1, 4096)),
                            dim3(256), 0, o->stream, A);
-        EJHIP(o, hipGetLastError());
-        EJHIP(o, hipStreamSynchronize(o->stream));
-        hipFree(S->head);
-        hipFree(S->next);
-        hipFree(S->vals);
-        hipFree(S->ts);
-        hipFree(S->cnt);
-        hipFree(S->cursor);
-        S->head = fresh.head;
-        S->next = fresh.next;
-        S->vals = fresh.vals;
-        S->ts = fresh.ts;
-        S->cnt = fresh.cnt;
-        S->cursor = fresh.cursor;
+        HIP_CHECK(o, hipGetLastError());
+        HIP_CHECK(o, hipStreamSynchronize(o->stream));
+        o->release(S->head);
+        o->release(S->next);
+        o->release(S->vals);
+        o->release(S->ts);
+        o->release(S->cnt);
+        o->release(S->cursor);
+        *S = fresh;
     }
-    return ej_check_err(o);
+    return op_check_err(o, ej_err_msg);
 }
 
 API int arroyo_amd_expjoin_checkpoint_drain(void *h, int32_t side,
                                             AmdOutBatch *out) {
     GpuExpJoin *o = (GpuExpJoin *)h;
-    if (ej_check_err(o)) return 1;
+    if (op_check_err(o, ej_err_msg)) return 1;
     SideMap *S = &o->side[side];
     int ncols = 1 + S->nv + 1;
-    EJHIP(o, hipMemsetAsync(o->d_n_out, 0, 8, o->stream));
+    HIP_CHECK(o, hipMemsetAsync(o->d_n_out, 0, 8, o->stream));
     EDrainArgs D = {};
     D.side = *S;
     for (int i = 0; i < ncols; i++) D.out[i] = o->d_out[i];
     D.n_out = o->d_n_out;
     D.out_cap = o->out_cap;
     D.err = o->d_err;
-    hipLaunchKernelGGL(k_ej_drain, dim3(ej_grid((int64_t)S->C + 1)),
+    hipLaunchKernelGGL(k_ej_drain, dim3(grid_for((int64_t)S->C + 1, 4096)),
                        dim3(256), 0, o->stream, D);
-    EJHIP(o, hipGetLastError());
+    HIP_CHECK(o, hipGetLastError());
     unsigned long long n = 0;
-    EJHIP(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
-                            o->stream));
-    EJHIP(o, hipStreamSynchronize(o->stream));
-    if (ej_check_err(o)) return 1;
-    memset(out, 0, sizeof *out);
-    out->n_rows = (int64_t)n;
-    out->n_cols = ncols;
-    out->cols = (void **)calloc(ncols, sizeof(void *));
-    out->is_f64 = (int32_t *)calloc(ncols, sizeof(int32_t));
-    for (int i = 0; i < ncols; i++) {
-        out->cols[i] = malloc((size_t)(n ? n : 1) * 8);
-        if (n)
-            EJHIP(o, hipMemcpyAsync(out->cols[i], o->d_out[i], (size_t)n * 8,
-                                    hipMemcpyDeviceToHost, o->stream));
-    }
-    EJHIP(o, hipStreamSynchronize(o->stream));
-    return 0;
+    HIP_CHECK(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
+                                o->stream));
+    HIP_CHECK(o, hipStreamSynchronize(o->stream));
+    if (op_check_err(o, ej_err_msg)) return 1;
+    return op_out_alloc(o, out, (int64_t)n, ncols, __func__) ||
+           out_copy_cols(o, out, o->d_out, (int64_t)n);
 }
 
 API int arroyo_amd_expjoin_restore(void *h, int32_t side,
@@ -988,29 +857,9 @@ API int arroyo_amd_expjoin_restore(void *h, int32_t side,
         o->has_wm = 1;
         if (watermark_nanos > o->wm) o->wm = watermark_nanos;
     }
-    return ej_check_err(o);
+    return op_check_err(o, ej_err_msg);
 }
 
 API void arroyo_amd_expjoin_destroy(void *h) {
-    GpuExpJoin *o = (GpuExpJoin *)h;
-    if (!o) return;
-    hipStreamSynchronize(o->stream);
-    for (int s = 0; s < 2; s++) ej_free_side(&o->side[s]);
-    hipFree(o->d_sortin);
-    hipFree(o->d_sortout);
-    hipFree(o->d_segs);
-    hipFree(o->d_nseg);
-    hipFree(o->d_ejtmp);
-    for (int i = 0; i < o->out_cols; i++) hipFree(o->d_out[i]);
-    hipFree(o->d_n_out);
-    hipFree(o->d_err);
-    int max_in = 1 + (o->cfg.n_left_vals > o->cfg.n_right_vals
-                          ? o->cfg.n_left_vals
-                          : o->cfg.n_right_vals) + 1;
-    for (int c = 0; c < max_in; c++) {
-        hipHostFree(o->stg_h[c]);
-        hipFree(o->stg_d[c]);
-    }
-    hipStreamDestroy(o->stream);
-    delete o;
+    delete (GpuExpJoin *)h;   /* ~OpBase drains the stream first */
 }

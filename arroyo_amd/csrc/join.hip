@@ -1,57 +1,8 @@
 /* arroyo-amd instant (windowed stream-stream) join, behind the
- * arroyo_amd_join_* C ABI (include/arroyo_amd.h).  Self-contained like the
- * other operator files: it carries its own copy of the few helpers it
- * shares with the window operator (arroyo_amd.hip). */
-#include <hip/hip_runtime.h>
-
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <algorithm>
+ * arroyo_amd_join_* C ABI (include/arroyo_amd.h). */
 #include <map>
-#include <vector>
 
-#include "../../include/arroyo_amd_types.h"
-
-#define API extern "C" __attribute__((visibility("default")))
-
-#define EMPTY_KEY  (-1LL)          /* all-0xFF bytes: memset-clearable */
-#define EMPTY_TAG  (~0ULL)
-#define ERR_TABLE_FULL    3
-
-__device__ inline uint64_t hash64(uint64_t x) {
-    x += 0x9e3779b97f4a7c15ULL;
-    x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ULL;
-    x = (x ^ (x >> 27)) * 0x94d049bb133111ebULL;
-    return x ^ (x >> 31);
-}
-
-/* claim-or-find a key slot in an open-addressing table (the build side's
- * key table); fullness is detected by probe length */
-#define MAX_PROBES 256u
-
-__device__ inline int64_t table_upsert(int64_t *keys, uint32_t C, int64_t key,
-                                       int *err) {
-    uint64_t m = C - 1;
-    uint64_t i = hash64((uint64_t)key) & m;
-    uint32_t lim = C < MAX_PROBES ? C : MAX_PROBES;
-    for (uint32_t probes = 0; probes < lim; probes++) {
-        int64_t k = keys[i];
-        if (k == key) return (int64_t)i;
-        if (k == EMPTY_KEY) {
-            int64_t old = (int64_t)atomicCAS((unsigned long long *)&keys[i],
-                                             (unsigned long long)EMPTY_KEY,
-                                             (unsigned long long)key);
-            if (old == EMPTY_KEY || old == key) return (int64_t)i;
-        }
-        i = (i + 1) & m;
-    }
-    *err = ERR_TABLE_FULL;
-    return -1;
-}
-
-/* create-time errors, before a handle exists (arroyo_amd_join_last_error) */
-static thread_local char g_err[512];
+#include "op_common.h"
 
 /* ================================================================== */
 /* Instant (windowed stream-stream) join: MI355X-native equivalent of
@@ -297,7 +248,7 @@ k_join_cross(JProbeArgs P, int64_t nl, int64_t out_base) {
         jemit_row(P, 0, i / P.nr, i % P.nr, out_base + i);
 }
 
-struct GpuJoin {
+struct GpuJoin : OpBase {
     AmdJoinConfig cfg;
     uint32_t I, cap, H;
     int64_t out_cap;
@@ -309,34 +260,19 @@ struct GpuJoin {
     uint32_t *l_hit;           /* [I*cap/32] matched-left bitmap (outer) */
     int64_t *d_out[16];
     unsigned long long *d_n_out;
-    int *d_err;
-    int64_t *stg[2][8];        /* pinned host + device staging per side */
-    int64_t *stg_d[2][8];
-    int64_t stg_cap;
+    Staging stg[2];            /* host-ingest staging per side */
     std::vector<std::vector<int64_t>> host_out;
     int out_cols;
     int has_wm; uint64_t wm;
     int64_t emitted_device_rows;
-    hipStream_t stream;
-    char err_msg[512];
 };
-
-#define JHIP(o, call)                                                         \
-    do {                                                                      \
-        hipError_t _e = (call);                                               \
-        if (_e != hipSuccess) {                                               \
-            snprintf((o)->err_msg, sizeof (o)->err_msg, "%s:%d hip: %s",      \
-                     __FILE__, __LINE__, hipGetErrorString(_e));              \
-            return 1;                                                         \
-        }                                                                     \
-    } while (0)
 
 API void *arroyo_amd_join_create(const AmdJoinConfig *cfg) {
     if (!cfg || cfg->n_keys < 0 || cfg->n_keys > 1 || cfg->n_left_vals < 0 ||
         cfg->n_right_vals < 0 || cfg->n_left_vals > 4 ||
         cfg->n_right_vals > 4 || cfg->join_type < 0 ||
         cfg->join_type > AMD_JOIN_FULL) {
-        snprintf(g_err, sizeof g_err, "invalid join config");
+        snprintf(g_create_err, sizeof g_create_err, "invalid join config");
         return nullptr;
     }
     GpuJoin *o = new GpuJoin();
@@ -348,79 +284,51 @@ API void *arroyo_amd_join_create(const AmdJoinConfig *cfg) {
     o->out_cols = cfg->n_keys + cfg->n_left_vals + cfg->n_right_vals + 1 +
                   (cfg->join_type != AMD_JOIN_INNER ? 2 : 0);
     if (hipSetDevice(cfg->device) != hipSuccess) {
-        snprintf(g_err, sizeof g_err,
+        snprintf(g_create_err, sizeof g_create_err,
                  "hipSetDevice(%d) failed: no HIP device (no CPU fallback)",
                  cfg->device);
         delete o;
         return nullptr;
     }
-    hipError_t e;
-    auto fail = [&](const char *what, hipError_t e2) {
-        snprintf(g_err, sizeof g_err, "%s: %s", what, hipGetErrorString(e2));
-        delete o;
-        return nullptr;
-    };
-#define JALLOC(p, bytes)                                                      \
-    if ((e = hipMalloc((void **)&(p), (bytes))) != hipSuccess)                \
-        return fail(#p, e);
     size_t plane = (size_t)o->I * o->cap;
-    JALLOC(o->tag, (size_t)o->I * 8);
+    OP_ALLOC(o, o->tag, (size_t)o->I * 8, 0xFF);
     for (int s = 0; s < 2; s++) {
         int nv = s == 0 ? cfg->n_left_vals : cfg->n_right_vals;
-        JALLOC(o->cursor[s], (size_t)o->I * 8);
-        if (cfg->n_keys) JALLOC(o->key[s], plane * 8);
-        if (nv) JALLOC(o->vals[s], (size_t)nv * plane * 8);
+        OP_ALLOC(o, o->cursor[s], (size_t)o->I * 8, 0);
+        if (cfg->n_keys) OP_ALLOC(o, o->key[s], plane * 8);
+        if (nv) OP_ALLOC(o, o->vals[s], (size_t)nv * plane * 8);
     }
-    JALLOC(o->b_keys, (size_t)o->H * 8);
-    JALLOC(o->b_head, (size_t)o->H * 4);
-    JALLOC(o->b_next, (size_t)o->I * o->cap * 4);
+    OP_ALLOC(o, o->b_keys, (size_t)o->H * 8);
+    OP_ALLOC(o, o->b_head, (size_t)o->H * 4);
+    OP_ALLOC(o, o->b_next, (size_t)o->I * o->cap * 4);
     if (cfg->join_type == AMD_JOIN_LEFT || cfg->join_type == AMD_JOIN_FULL)
-        JALLOC(o->l_hit, plane / 32 * 4 + 4);
+        OP_ALLOC(o, o->l_hit, plane / 32 * 4 + 4);
     for (int i = 0; i < o->out_cols && i < 16; i++)
-        JALLOC(o->d_out[i], (size_t)o->out_cap * 8);
-    JALLOC(o->d_n_out, 8);
-    JALLOC(o->d_err, 4);
-#undef JALLOC
-    hipMemset(o->tag, 0xFF, (size_t)o->I * 8);
-    for (int s = 0; s < 2; s++)
-        hipMemset(o->cursor[s], 0, (size_t)o->I * 8);
-    hipMemset(o->d_err, 0, 4);
-    hipStreamCreate(&o->stream);
-    o->stg_cap = 1 << 20;
+        OP_ALLOC(o, o->d_out[i], (size_t)o->out_cap * 8);
+    OP_ALLOC(o, o->d_n_out, 8);
+    OP_ALLOC(o, o->d_err, 4, 0);
+    OP_TRY(o, "hipStreamCreate", o->stream_create(&o->stream));
     for (int s = 0; s < 2; s++) {
-        int nc = cfg->n_keys + (s == 0 ? cfg->n_left_vals : cfg->n_right_vals) + 1;
-        for (int c = 0; c < nc; c++) {
-            if (hipHostMalloc((void **)&o->stg[s][c], (size_t)o->stg_cap * 8) !=
-                    hipSuccess ||
-                hipMalloc((void **)&o->stg_d[s][c], (size_t)o->stg_cap * 8) !=
-                    hipSuccess) {
-                snprintf(g_err, sizeof g_err, "join staging alloc failed");
-                delete o;
-                return nullptr;
-            }
-        }
+        int nv = s == 0 ? cfg->n_left_vals : cfg->n_right_vals;
+        OP_TRY_MSG(o, "join staging alloc failed",
+                   o->stg[s].alloc(o, cfg->n_keys + nv + 1, 1 << 20));
     }
     o->host_out.resize(o->out_cols);
     return o;
 }
 
 API const char *arroyo_amd_join_last_error(void *h) {
-    return h ? ((GpuJoin *)h)->err_msg : g_err;
+    return h ? ((GpuJoin *)h)->err_msg : g_create_err;
 }
 
-static int join_check_err(GpuJoin *o) {
-    int e = 0;
-    JHIP(o, hipMemcpyAsync(&e, o->d_err, 4, hipMemcpyDeviceToHost, o->stream));
-    JHIP(o, hipStreamSynchronize(o->stream));
-    if (!e) return 0;
-    const char *msg = e == JERR_LATE      ? "batch timestamp before watermark"
-                      : e == JERR_INSTANTS ? "live-instant table full; raise instants"
-                      : e == JERR_ROWS_CAP ? "per-instant row buffer full; raise log2_rows_cap"
-                      : e == JERR_OUT_CAP  ? "output buffer full; raise log2_out_cap"
-                      : e == ERR_TABLE_FULL ? "join build table full"
-                                            : "device error";
-    snprintf(o->err_msg, sizeof o->err_msg, "%s", msg);
-    return 1;
+static const char *join_err_msg(int e) {
+    return e == JERR_LATE       ? "batch timestamp before watermark"
+           : e == JERR_INSTANTS ? "live-instant table full; raise instants"
+           : e == JERR_ROWS_CAP
+               ? "per-instant row buffer full; raise log2_rows_cap"
+           : e == JERR_OUT_CAP   ? "output buffer full; raise log2_out_cap"
+           : e == ERR_TABLE_FULL ? "join build table full"
+                                 : "device error";
 }
 
 static int join_append_device(GpuJoin *o, int side, const int64_t *const *dcols,
@@ -441,10 +349,9 @@ static int join_append_device(GpuJoin *o, int side, const int64_t *const *dcols,
     A.has_wm = o->has_wm;
     A.wm = o->wm;
     A.err = o->d_err;
-    int64_t want = (n_rows + 255) / 256;
-    int blocks = (int)(want > 1024 ? 1024 : (want < 1 ? 1 : want));
+    int blocks = grid_for(n_rows, 1024);
     hipLaunchKernelGGL(k_join_append, dim3(blocks), dim3(256), 0, o->stream, A);
-    JHIP(o, hipGetLastError());
+    HIP_CHECK(o, hipGetLastError());
     return 0;
 }
 
@@ -461,18 +368,13 @@ API int arroyo_amd_join_process_batch(void *h, int32_t side,
     int64_t done = 0;
     while (done < n_rows) {
         int64_t take = n_rows - done;
-        if (take > o->stg_cap) take = o->stg_cap;
+        if (take > o->stg[side].cap) take = o->stg[side].cap;
         const int64_t *dcols[6];
-        for (int c = 0; c < n_cols; c++) {
-            memcpy(o->stg[side][c], cols[c] + done, (size_t)take * 8);
-            JHIP(o, hipMemcpyAsync(o->stg_d[side][c], o->stg[side][c],
-                                   (size_t)take * 8, hipMemcpyHostToDevice,
-                                   o->stream));
-            dcols[c] = o->stg_d[side][c];
-        }
-        if (join_append_device(o, side, dcols, take)) return 1;
+        if (o->stg[side].stage_chunk(o, cols, n_cols, done, take, dcols) ||
+            join_append_device(o, side, dcols, take))
+            return 1;
         /* staging reused next iteration: wait for this append to finish */
-        JHIP(o, hipStreamSynchronize(o->stream));
+        HIP_CHECK(o, hipStreamSynchronize(o->stream));
         done += take;
     }
     return 0;
@@ -500,7 +402,7 @@ static int join_fire(GpuJoin *o, uint64_t instant,
                      const std::vector<unsigned long long> &c0,
                      const std::vector<unsigned long long> &c1) {
     size_t plane = (size_t)o->I * o->cap;
-    JHIP(o, hipMemsetAsync(o->d_n_out, 0, 8, o->stream));
+    HIP_CHECK(o, hipMemsetAsync(o->d_n_out, 0, 8, o->stream));
     JProbeArgs P = {};
     P.l_vals = o->vals[0];
     P.r_vals = o->vals[1];
@@ -533,16 +435,16 @@ static int join_fire(GpuJoin *o, uint64_t instant,
             if (!c0[ls]) continue;
             int64_t base = (int64_t)ls * o->cap;
             if (!use_bitmap)
-                JHIP(o, hipMemsetAsync(o->l_hit + base / 32, 0,
-                                       (size_t)o->cap / 32 * 4, o->stream));
+                HIP_CHECK(o, hipMemsetAsync(o->l_hit + base / 32, 0,
+                                            (size_t)o->cap / 32 * 4,
+                                            o->stream));
             JProbeArgs Q = P;
             Q.l_off = 0;
             Q.l_hit = o->l_hit;
-            int64_t want = ((int64_t)c0[ls] + 255) / 256;
-            int blocks = (int)(want > 1024 ? 1024 : (want < 1 ? 1 : want));
+            int blocks = grid_for((int64_t)c0[ls], 1024);
             hipLaunchKernelGGL(k_join_unmatched_left, dim3(blocks), dim3(256),
                                0, o->stream, Q, base, (int64_t)c0[ls]);
-            JHIP(o, hipGetLastError());
+            HIP_CHECK(o, hipGetLastError());
         }
         return 0;
     };
@@ -563,20 +465,18 @@ static int join_fire(GpuJoin *o, uint64_t instant,
                     P.l_off = (size_t)ls * o->cap;
                     P.r_off = (size_t)rs * o->cap;
                     P.nr = (int64_t)c1[rs];
-                    int64_t want = (pair + 255) / 256;
-                    int blocks =
-                        (int)(want > 1024 ? 1024 : (want < 1 ? 1 : want));
+                    int blocks = grid_for(pair, 1024);
                     hipLaunchKernelGGL(k_join_cross, dim3(blocks), dim3(256),
                                        0, o->stream, P, (int64_t)c0[ls], base);
-                    JHIP(o, hipGetLastError());
+                    HIP_CHECK(o, hipGetLastError());
                     base += pair;
                 }
             }
             n = (unsigned long long)total;
         } else if (nl && emit_l) {
             if (pad_left_slots(false)) return 1;
-            JHIP(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
-                                   o->stream));
+            HIP_CHECK(o, hipMemcpyAsync(&n, o->d_n_out, 8,
+                                        hipMemcpyDeviceToHost, o->stream));
         } else if (nr && emit_r) {
             /* no key plane exists when n_keys == 0: pad the right rows
              * directly instead of probing */
@@ -584,22 +484,21 @@ static int join_fire(GpuJoin *o, uint64_t instant,
                 if (!c1[rs]) continue;
                 P.r_off = (size_t)rs * o->cap;
                 P.nr = (int64_t)c1[rs];
-                int64_t want = (P.nr + 255) / 256;
-                int blocks = (int)(want > 1024 ? 1024 : want);
+                int blocks = grid_for(P.nr, 1024);
                 hipLaunchKernelGGL(k_join_pad_right, dim3(blocks), dim3(256),
                                    0, o->stream, P);
-                JHIP(o, hipGetLastError());
+                HIP_CHECK(o, hipGetLastError());
             }
-            JHIP(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
-                                   o->stream));
+            HIP_CHECK(o, hipMemcpyAsync(&n, o->d_n_out, 8,
+                                        hipMemcpyDeviceToHost, o->stream));
         }
     } else if ((nl && nr) || (nl && emit_l) || (nr && emit_r)) {
         bool probes = nr && (nl || emit_r);
         if (probes || nl) {
-            JHIP(o, hipMemsetAsync(o->b_keys, 0xFF, (size_t)o->H * 8,
-                                   o->stream));
-            JHIP(o, hipMemsetAsync(o->b_head, 0xFF, (size_t)o->H * 4,
-                                   o->stream));
+            HIP_CHECK(o, hipMemsetAsync(o->b_keys, 0xFF, (size_t)o->H * 8,
+                                        o->stream));
+            HIP_CHECK(o, hipMemsetAsync(o->b_head, 0xFF, (size_t)o->H * 4,
+                                        o->stream));
         }
         for (uint32_t ls : slots) {
             if (!c0[ls]) continue;
@@ -612,18 +511,17 @@ static int join_fire(GpuJoin *o, uint64_t instant,
             B.b_next = o->b_next;
             B.H = o->H;
             B.err = o->d_err;
-            int64_t want = (B.nl + 255) / 256;
-            int blocks = (int)(want > 1024 ? 1024 : want);
+            int blocks = grid_for(B.nl, 1024);
             hipLaunchKernelGGL(k_join_build, dim3(blocks), dim3(256), 0,
                                o->stream, B);
-            JHIP(o, hipGetLastError());
+            HIP_CHECK(o, hipGetLastError());
         }
         if (emit_l)
             for (uint32_t ls : slots) {
                 if (!c0[ls]) continue;
-                JHIP(o, hipMemsetAsync(
-                            o->l_hit + (size_t)ls * o->cap / 32, 0,
-                            (size_t)o->cap / 32 * 4, o->stream));
+                HIP_CHECK(o, hipMemsetAsync(
+                                 o->l_hit + (size_t)ls * o->cap / 32, 0,
+                                 (size_t)o->cap / 32 * 4, o->stream));
             }
         /* chain links are global row indices: probe reads left values at
          * l_vals[v*plane + li] directly, so l_off = 0 */
@@ -635,23 +533,22 @@ static int join_fire(GpuJoin *o, uint64_t instant,
                 P.r_key = o->key[1] + (size_t)rs * o->cap;
                 P.r_off = (size_t)rs * o->cap;
                 P.nr = (int64_t)c1[rs];
-                int64_t want = (P.nr + 255) / 256;
-                int blocks = (int)(want > 1024 ? 1024 : want);
+                int blocks = grid_for(P.nr, 1024);
                 hipLaunchKernelGGL(k_join_probe, dim3(blocks), dim3(256), 0,
                                    o->stream, P);
-                JHIP(o, hipGetLastError());
+                HIP_CHECK(o, hipGetLastError());
             }
         if (emit_l && nl && pad_left_slots(true)) return 1;
-        JHIP(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
-                               o->stream));
+        HIP_CHECK(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
+                                    o->stream));
     }
     /* retire every slot of the instant */
     for (uint32_t s : slots) {
-        JHIP(o, hipMemsetAsync(o->tag + s, 0xFF, 8, o->stream));
-        JHIP(o, hipMemsetAsync(o->cursor[0] + s, 0, 8, o->stream));
-        JHIP(o, hipMemsetAsync(o->cursor[1] + s, 0, 8, o->stream));
+        HIP_CHECK(o, hipMemsetAsync(o->tag + s, 0xFF, 8, o->stream));
+        HIP_CHECK(o, hipMemsetAsync(o->cursor[0] + s, 0, 8, o->stream));
+        HIP_CHECK(o, hipMemsetAsync(o->cursor[1] + s, 0, 8, o->stream));
     }
-    JHIP(o, hipStreamSynchronize(o->stream));
+    HIP_CHECK(o, hipStreamSynchronize(o->stream));
     if (n == 0) return 0;
     if ((int64_t)n > o->out_cap) {
         snprintf(o->err_msg, sizeof o->err_msg,
@@ -662,11 +559,11 @@ static int join_fire(GpuJoin *o, uint64_t instant,
         for (int i = 0; i < o->out_cols; i++) {
             size_t old = o->host_out[i].size();
             o->host_out[i].resize(old + n);
-            JHIP(o, hipMemcpyAsync(o->host_out[i].data() + old, o->d_out[i],
-                                   (size_t)n * 8, hipMemcpyDeviceToHost,
-                                   o->stream));
+            HIP_CHECK(o, hipMemcpyAsync(o->host_out[i].data() + old,
+                                        o->d_out[i], (size_t)n * 8,
+                                        hipMemcpyDeviceToHost, o->stream));
         }
-        JHIP(o, hipStreamSynchronize(o->stream));
+        HIP_CHECK(o, hipStreamSynchronize(o->stream));
     } else {
         o->emitted_device_rows += (int64_t)n;
     }
@@ -677,43 +574,41 @@ static int join_fire(GpuJoin *o, uint64_t instant,
 /* Arrow validity bitmaps for null-padded value columns (LSB bit order,
  * see AmdOutBatch doc): left vals valid where the left-presence column is
  * set, right vals likewise.  The presence columns stay in the output. */
-static void fill_join_validity(AmdOutBatch *out, int base_l, int nlv,
-                               int nrv, int lp_col, int rp_col) {
+static int fill_join_validity(AmdOutBatch *out, int base_l, int nlv,
+                              int nrv, int lp_col, int rp_col) {
     int64_t n = out->n_rows;
-    out->validity = (uint8_t **)calloc(out->n_cols, sizeof(uint8_t *));
-    if (!out->validity || n == 0) return;
-    size_t nbytes = (size_t)((n + 7) / 8);
-    for (int g = 0; g < 2; g++) {
+    if (out_alloc_validity(out)) return 1;
+    for (int g = 0; n && g < 2; g++) {
         int base = g == 0 ? base_l : base_l + nlv;
         int cnt = g == 0 ? nlv : nrv;
         const int64_t *pres =
             (const int64_t *)out->cols[g == 0 ? lp_col : rp_col];
         for (int c = base; c < base + cnt; c++) {
-            uint8_t *bm = (uint8_t *)calloc(nbytes, 1);
-            if (!bm) continue;
+            uint8_t *bm = out_validity_col(out, c);
+            if (!bm) return 1;
             for (int64_t r = 0; r < n; r++)
                 if (pres[r]) bm[r >> 3] |= (uint8_t)(1u << (r & 7));
-            out->validity[c] = bm;
         }
     }
+    return 0;
 }
 
 API int arroyo_amd_join_handle_watermark(void *h, uint64_t wm,
                                          AmdOutBatch *out) {
     GpuJoin *o = (GpuJoin *)h;
-    if (join_check_err(o)) return 1;
+    if (op_check_err(o, join_err_msg)) return 1;
     o->has_wm = 1;
     o->wm = wm;
     /* snapshot live instants + row counts */
     std::vector<uint64_t> tags(o->I);
     std::vector<unsigned long long> c0(o->I), c1(o->I);
-    JHIP(o, hipMemcpyAsync(tags.data(), o->tag, (size_t)o->I * 8,
-                           hipMemcpyDeviceToHost, o->stream));
-    JHIP(o, hipMemcpyAsync(c0.data(), o->cursor[0], (size_t)o->I * 8,
-                           hipMemcpyDeviceToHost, o->stream));
-    JHIP(o, hipMemcpyAsync(c1.data(), o->cursor[1], (size_t)o->I * 8,
-                           hipMemcpyDeviceToHost, o->stream));
-    JHIP(o, hipStreamSynchronize(o->stream));
+    HIP_CHECK(o, hipMemcpyAsync(tags.data(), o->tag, (size_t)o->I * 8,
+                                hipMemcpyDeviceToHost, o->stream));
+    HIP_CHECK(o, hipMemcpyAsync(c0.data(), o->cursor[0], (size_t)o->I * 8,
+                                hipMemcpyDeviceToHost, o->stream));
+    HIP_CHECK(o, hipMemcpyAsync(c1.data(), o->cursor[1], (size_t)o->I * 8,
+                                hipMemcpyDeviceToHost, o->stream));
+    HIP_CHECK(o, hipStreamSynchronize(o->stream));
     /* timestamp order (instant_join.rs:265-281); an instant may occupy
      * several slots after recycling — fire them as one group */
     std::map<uint64_t, std::vector<uint32_t>> fired;
@@ -723,22 +618,21 @@ API int arroyo_amd_join_handle_watermark(void *h, uint64_t wm,
         if (join_fire(o, kv.first, kv.second, c0, c1))
             return 1;
     if (out) {
-        memset(out, 0, sizeof *out);
         int64_t n = o->host_out.empty() ? 0 : (int64_t)o->host_out[0].size();
-        out->n_rows = n;
-        out->n_cols = o->out_cols;
-        out->cols = (void **)calloc(o->out_cols, sizeof(void *));
-        out->is_f64 = (int32_t *)calloc(o->out_cols, sizeof(int32_t));
-        for (int i = 0; i < o->out_cols; i++) {
-            out->cols[i] = malloc((size_t)(n ? n : 1) * 8);
-            if (n) memcpy(out->cols[i], o->host_out[i].data(), (size_t)n * 8);
-        }
+        if (op_out_alloc(o, out, n, o->out_cols, __func__)) return 1;
+        for (int i = 0; n && i < o->out_cols; i++)
+            memcpy(out->cols[i], o->host_out[i].data(), (size_t)n * 8);
         if (o->cfg.join_type != AMD_JOIN_INNER) {
             /* [key?, lvals, rvals, instant, lp, rp] */
             int base_l = o->cfg.n_keys;
             int inst = base_l + o->cfg.n_left_vals + o->cfg.n_right_vals;
-            fill_join_validity(out, base_l, o->cfg.n_left_vals,
-                               o->cfg.n_right_vals, inst + 1, inst + 2);
+            if (fill_join_validity(out, base_l, o->cfg.n_left_vals,
+                                   o->cfg.n_right_vals, inst + 1, inst + 2)) {
+                out_free_host(out);
+                snprintf(o->err_msg, sizeof o->err_msg,
+                         "validity bitmap allocation failed");
+                return 1;
+            }
         }
         for (auto &v : o->host_out) v.clear();
     }
@@ -749,26 +643,20 @@ API int arroyo_amd_join_handle_watermark(void *h, uint64_t wm,
 API int arroyo_amd_join_checkpoint_drain(void *h, int32_t side,
                                          AmdOutBatch *out) {
     GpuJoin *o = (GpuJoin *)h;
-    if (join_check_err(o)) return 1;
+    if (op_check_err(o, join_err_msg)) return 1;
     int nv = side == 0 ? o->cfg.n_left_vals : o->cfg.n_right_vals;
     int ncols = o->cfg.n_keys + nv + 1;
     std::vector<uint64_t> tags(o->I);
     std::vector<unsigned long long> cur(o->I);
-    JHIP(o, hipMemcpyAsync(tags.data(), o->tag, (size_t)o->I * 8,
-                           hipMemcpyDeviceToHost, o->stream));
-    JHIP(o, hipMemcpyAsync(cur.data(), o->cursor[side], (size_t)o->I * 8,
-                           hipMemcpyDeviceToHost, o->stream));
-    JHIP(o, hipStreamSynchronize(o->stream));
+    HIP_CHECK(o, hipMemcpyAsync(tags.data(), o->tag, (size_t)o->I * 8,
+                                hipMemcpyDeviceToHost, o->stream));
+    HIP_CHECK(o, hipMemcpyAsync(cur.data(), o->cursor[side], (size_t)o->I * 8,
+                                hipMemcpyDeviceToHost, o->stream));
+    HIP_CHECK(o, hipStreamSynchronize(o->stream));
     int64_t total = 0;
     for (uint32_t s = 0; s < o->I; s++)
         if (tags[s] != EMPTY_TAG) total += (int64_t)cur[s];
-    memset(out, 0, sizeof *out);
-    out->n_rows = total;
-    out->n_cols = ncols;
-    out->cols = (void **)calloc(ncols, sizeof(void *));
-    out->is_f64 = (int32_t *)calloc(ncols, sizeof(int32_t));
-    for (int i = 0; i < ncols; i++)
-        out->cols[i] = malloc((size_t)(total ? total : 1) * 8);
+    if (op_out_alloc(o, out, total, ncols, __func__)) return 1;
     size_t plane = (size_t)o->I * o->cap;
     int64_t r = 0;
     for (uint32_t s = 0; s < o->I; s++) {
@@ -776,18 +664,18 @@ API int arroyo_amd_join_checkpoint_drain(void *h, int32_t side,
         int64_t n = (int64_t)cur[s];
         int col = 0;
         if (o->cfg.n_keys) {
-            JHIP(o, hipMemcpyAsync((int64_t *)out->cols[col] + r,
-                                   o->key[side] + (size_t)s * o->cap,
-                                   (size_t)n * 8, hipMemcpyDeviceToHost,
-                                   o->stream));
+            HIP_CHECK(o, hipMemcpyAsync((int64_t *)out->cols[col] + r,
+                                        o->key[side] + (size_t)s * o->cap,
+                                        (size_t)n * 8, hipMemcpyDeviceToHost,
+                                        o->stream));
             col++;
         }
         for (int v = 0; v < nv; v++, col++)
-            JHIP(o, hipMemcpyAsync(
-                        (int64_t *)out->cols[col] + r,
-                        o->vals[side] + (size_t)v * plane + (size_t)s * o->cap,
-                        (size_t)n * 8, hipMemcpyDeviceToHost, o->stream));
-        JHIP(o, hipStreamSynchronize(o->stream));
+            HIP_CHECK(o, hipMemcpyAsync(
+                    (int64_t *)out->cols[col] + r,
+                    o->vals[side] + (size_t)v * plane + (size_t)s * o->cap,
+                    (size_t)n * 8, hipMemcpyDeviceToHost, o->stream));
+        HIP_CHECK(o, hipStreamSynchronize(o->stream));
         for (int64_t j = 0; j < n; j++)
             ((int64_t *)out->cols[ncols - 1])[r + j] = (int64_t)tags[s];
         r += n;
@@ -796,28 +684,5 @@ API int arroyo_amd_join_checkpoint_drain(void *h, int32_t side,
 }
 
 API void arroyo_amd_join_destroy(void *h) {
-    GpuJoin *o = (GpuJoin *)h;
-    if (!o) return;
-    hipStreamSynchronize(o->stream);
-    hipFree(o->tag);
-    for (int s = 0; s < 2; s++) {
-        hipFree(o->cursor[s]);
-        hipFree(o->key[s]);
-        hipFree(o->vals[s]);
-        int nc = o->cfg.n_keys +
-                 (s == 0 ? o->cfg.n_left_vals : o->cfg.n_right_vals) + 1;
-        for (int c = 0; c < nc; c++) {
-            hipHostFree(o->stg[s][c]);
-            hipFree(o->stg_d[s][c]);
-        }
-    }
-    hipFree(o->b_keys);
-    hipFree(o->b_head);
-    hipFree(o->b_next);
-    hipFree(o->l_hit);
-    for (int i = 0; i < o->out_cols && i < 16; i++) hipFree(o->d_out[i]);
-    hipFree(o->d_n_out);
-    hipFree(o->d_err);
-    hipStreamDestroy(o->stream);
-    delete o;
+    delete (GpuJoin *)h;   /* ~OpBase drains the stream first */
 }

@@ -15,16 +15,9 @@
  * Parity is pinned against oracle/arroyo_oracle.c by tests/test_mapop.py
  * (bit-exact, including the f64 bit patterns).
  */
-#include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-
-#include "../../include/arroyo_amd_types.h"
-
-#define API extern "C" __attribute__((visibility("default")))
+#include "op_common.h"
 
 namespace mapop {
 
@@ -117,9 +110,8 @@ k_map_scatter(const int64_t *keep, const int64_t *pos,
 
 using namespace mapop;
 
-static char g_map_err[256];
 
-struct GpuMap {
+struct GpuMap : OpBase {
     AmdMapConfig cfg;
     int64_t cap;               /* per-batch row capacity */
     int64_t *d_vals[AMD_MAP_MAX_OUT];
@@ -127,28 +119,15 @@ struct GpuMap {
     int64_t *d_keep, *d_pos;
     void *cub_tmp;
     size_t cub_bytes;
-    int *d_err;
-    int64_t *stg_h[AMD_MAP_MAX_REGS], *stg_d[AMD_MAP_MAX_REGS];
-    hipStream_t stream;
-    char err_msg[512];
+    Staging stg;
 };
-
-#define MHIP(o, call)                                                         \
-    do {                                                                      \
-        hipError_t _e = (call);                                               \
-        if (_e != hipSuccess) {                                               \
-            snprintf((o)->err_msg, sizeof (o)->err_msg, "%s:%d hip: %s",      \
-                     __FILE__, __LINE__, hipGetErrorString(_e));              \
-            return 1;                                                         \
-        }                                                                     \
-    } while (0)
 
 API void *arroyo_amd_map_create(const AmdMapConfig *cfg) {
     if (!cfg || cfg->n_in_cols < 1 || cfg->n_in_cols > AMD_MAP_MAX_REGS ||
         cfg->n_prog < 0 || cfg->n_prog > AMD_MAP_MAX_PROG ||
         cfg->n_out < 1 || cfg->n_out > 6 ||
         cfg->filter_reg >= AMD_MAP_MAX_REGS) {
-        snprintf(g_map_err, sizeof g_map_err,
+        snprintf(g_create_err, sizeof g_create_err,
                  "invalid map config (n_out <= 6 on the GPU path)");
         return nullptr;
     }
@@ -156,154 +135,133 @@ API void *arroyo_amd_map_create(const AmdMapConfig *cfg) {
         if (cfg->prog[i].dst < 0 || cfg->prog[i].dst >= AMD_MAP_MAX_REGS ||
             cfg->prog[i].a < 0 || cfg->prog[i].a >= AMD_MAP_MAX_REGS ||
             cfg->prog[i].b < 0 || cfg->prog[i].b >= AMD_MAP_MAX_REGS) {
-            snprintf(g_map_err, sizeof g_map_err, "invalid map program");
+            snprintf(g_create_err, sizeof g_create_err, "invalid map program");
             return nullptr;
         }
     GpuMap *o = new GpuMap();
     o->cfg = *cfg;
     o->cap = 1 << 20;
     if (hipSetDevice(cfg->device) != hipSuccess) {
-        snprintf(g_map_err, sizeof g_map_err,
+        snprintf(g_create_err, sizeof g_create_err,
                  "hipSetDevice(%d) failed: no HIP device (no CPU fallback)",
                  cfg->device);
         delete o;
         return nullptr;
     }
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < cfg->n_out && e == hipSuccess; i++) {
-        e = hipMalloc((void **)&o->d_vals[i], (size_t)o->cap * 8);
-        if (e == hipSuccess)
-            e = hipMalloc((void **)&o->d_out[i], (size_t)o->cap * 8);
+    for (int i = 0; i < cfg->n_out; i++) {
+        OP_TRY(o, "map alloc", o->dev_alloc(o->d_vals[i], (size_t)o->cap * 8));
+        OP_TRY(o, "map alloc", o->dev_alloc(o->d_out[i], (size_t)o->cap * 8));
     }
-    if (e == hipSuccess) e = hipMalloc((void **)&o->d_keep, (size_t)o->cap * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&o->d_pos, (size_t)o->cap * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&o->d_err, 4);
-    for (int c = 0; c < cfg->n_in_cols && e == hipSuccess; c++) {
-        if (hipHostMalloc((void **)&o->stg_h[c], (size_t)o->cap * 8) !=
-                hipSuccess ||
-            hipMalloc((void **)&o->stg_d[c], (size_t)o->cap * 8) !=
-                hipSuccess)
-            e = hipErrorOutOfMemory;
-    }
-    if (e != hipSuccess) {
-        snprintf(g_map_err, sizeof g_map_err, "map alloc: %s",
-                 hipGetErrorString(e));
-        delete o;
-        return nullptr;
-    }
+    OP_TRY(o, "map alloc", o->dev_alloc(o->d_keep, (size_t)o->cap * 8));
+    OP_TRY(o, "map alloc", o->dev_alloc(o->d_pos, (size_t)o->cap * 8));
+    OP_TRY(o, "map alloc", o->dev_alloc(o->d_err, 4, 0));
+    OP_TRY(o, "map alloc", o->stg.alloc(o, cfg->n_in_cols, o->cap));
     o->cub_bytes = 0;
-    hipcub::DeviceScan::ExclusiveSum(nullptr, o->cub_bytes, o->d_keep,
-                                     o->d_pos, (int)o->cap);
-    if (hipMalloc(&o->cub_tmp, o->cub_bytes ? o->cub_bytes : 1) !=
-        hipSuccess) {
-        snprintf(g_map_err, sizeof g_map_err, "map cub alloc failed");
-        delete o;
-        return nullptr;
-    }
-    hipMemset(o->d_err, 0, 4);
-    hipStreamCreate(&o->stream);
+    OP_TRY(o, "map cub size",
+           hipcub::DeviceScan::ExclusiveSum(nullptr, o->cub_bytes, o->d_keep,
+                                            o->d_pos, (int)o->cap));
+    OP_TRY_MSG(o, "map cub alloc failed",
+               o->dev_alloc(o->cub_tmp, o->cub_bytes ? o->cub_bytes : 1));
+    OP_TRY(o, "hipStreamCreate", o->stream_create(&o->stream));
     return o;
 }
 
 API const char *arroyo_amd_map_last_error(void *h) {
-    return h ? ((GpuMap *)h)->err_msg : g_map_err;
+    return h ? ((GpuMap *)h)->err_msg : g_create_err;
 }
 
-static int map_grid(int64_t want) {
-    int64_t w = (want + 255) / 256;
-    return (int)(w > 2048 ? 2048 : (w < 1 ? 1 : w));
+static const char *map_err_msg(int) { return "division by zero"; }
+
+/* evaluate the program over n_rows device rows, compact by the filter and
+ * read the error word.  src[i] = where output column i landed, *n_keep =
+ * surviving rows. */
+static int map_eval(GpuMap *o, const int64_t *const *dcols, int32_t n_cols,
+                    int64_t n_rows, const int64_t **src, int64_t *n_keep) {
+    const AmdMapConfig &c = o->cfg;
+    MapArgs A = {};
+    for (int cc = 0; cc < n_cols; cc++) A.cols[cc] = dcols[cc];
+    A.n_in = n_cols;
+    A.n_rows = n_rows;
+    A.cfg = c;
+    A.keep = c.filter_reg >= 0 ? o->d_keep : nullptr;
+    for (int i = 0; i < c.n_out; i++) src[i] = A.vals[i] = o->d_vals[i];
+    A.err = o->d_err;
+    hipLaunchKernelGGL(k_map_eval, dim3(grid_for(n_rows, 2048)), dim3(256), 0,
+                       o->stream, A);
+    HIP_CHECK(o, hipGetLastError());
+    *n_keep = n_rows;
+    if (c.filter_reg >= 0 && n_rows > 0) {
+        size_t tmp = o->cub_bytes;
+        HIP_CHECK(o, hipcub::DeviceScan::ExclusiveSum(
+                         o->cub_tmp, tmp, o->d_keep, o->d_pos, (int)n_rows,
+                         o->stream));
+        hipLaunchKernelGGL(
+            k_map_scatter, dim3(grid_for(n_rows, 2048)), dim3(256), 0,
+            o->stream, o->d_keep, o->d_pos, o->d_vals[0],
+            c.n_out > 1 ? o->d_vals[1] : nullptr,
+            c.n_out > 2 ? o->d_vals[2] : nullptr,
+            c.n_out > 3 ? o->d_vals[3] : nullptr,
+            c.n_out > 4 ? o->d_vals[4] : nullptr,
+            c.n_out > 5 ? o->d_vals[5] : nullptr, o->d_out[0],
+            c.n_out > 1 ? o->d_out[1] : nullptr,
+            c.n_out > 2 ? o->d_out[2] : nullptr,
+            c.n_out > 3 ? o->d_out[3] : nullptr,
+            c.n_out > 4 ? o->d_out[4] : nullptr,
+            c.n_out > 5 ? o->d_out[5] : nullptr, c.n_out, n_rows);
+        HIP_CHECK(o, hipGetLastError());
+        /* n_keep = pos[last] + keep[last] */
+        int64_t tail[2] = {0, 0};
+        HIP_CHECK(o, hipMemcpyAsync(&tail[0], o->d_pos + (n_rows - 1), 8,
+                                    hipMemcpyDeviceToHost, o->stream));
+        HIP_CHECK(o, hipMemcpyAsync(&tail[1], o->d_keep + (n_rows - 1), 8,
+                                    hipMemcpyDeviceToHost, o->stream));
+        HIP_CHECK(o, hipStreamSynchronize(o->stream));
+        *n_keep = tail[0] + tail[1];
+    }
+    if (c.filter_reg >= 0)
+        for (int i = 0; i < c.n_out; i++) src[i] = o->d_out[i];
+    return op_check_err(o, map_err_msg);
+}
+
+static int map_check_cols(GpuMap *o, int32_t n_cols) {
+    if (n_cols == o->cfg.n_in_cols) return 0;
+    snprintf(o->err_msg, sizeof o->err_msg, "expected %d cols, got %d",
+             o->cfg.n_in_cols, n_cols);
+    return 1;
 }
 
 static int map_run(GpuMap *o, const int64_t *const *cols, int32_t n_cols,
                    int64_t n_rows, AmdOutBatch *out) {
     const AmdMapConfig &c = o->cfg;
-    if (n_cols != c.n_in_cols) {
-        snprintf(o->err_msg, sizeof o->err_msg, "expected %d cols, got %d",
-                 c.n_in_cols, n_cols);
-        return 1;
-    }
-    memset(out, 0, sizeof *out);
-    out->n_cols = c.n_out;
-    out->cols = (void **)calloc(c.n_out, sizeof(void *));
-    out->is_f64 = (int32_t *)calloc(c.n_out, sizeof(int32_t));
+    if (map_check_cols(o, n_cols)) return 1;
+    /* room for every input row; n_rows is set to what survives */
+    if (op_out_alloc(o, out, n_rows, c.n_out, __func__)) return 1;
     for (int i = 0; i < c.n_out; i++) out->is_f64[i] = c.out_is_f64[i];
     int64_t emitted = 0;
     int64_t done = 0;
     while (done < n_rows) {
         int64_t take = n_rows - done;
         if (take > o->cap) take = o->cap;
-        MapArgs A = {};
-        for (int cc = 0; cc < n_cols; cc++) {
-            memcpy(o->stg_h[cc], cols[cc] + done, (size_t)take * 8);
-            MHIP(o, hipMemcpyAsync(o->stg_d[cc], o->stg_h[cc],
-                                   (size_t)take * 8, hipMemcpyHostToDevice,
-                                   o->stream));
-            A.cols[cc] = o->stg_d[cc];
-        }
-        A.n_in = n_cols;
-        A.n_rows = take;
-        A.cfg = c;
-        A.keep = c.filter_reg >= 0 ? o->d_keep : nullptr;
-        for (int i = 0; i < c.n_out; i++) A.vals[i] = o->d_vals[i];
-        A.err = o->d_err;
-        hipLaunchKernelGGL(k_map_eval, dim3(map_grid(take)), dim3(256), 0,
-                           o->stream, A);
-        MHIP(o, hipGetLastError());
-        int64_t n_keep = take;
-        const int64_t *src[AMD_MAP_MAX_OUT];
-        for (int i = 0; i < c.n_out; i++) src[i] = o->d_vals[i];
-        if (c.filter_reg >= 0) {
-            size_t tmp = o->cub_bytes;
-            hipcub::DeviceScan::ExclusiveSum(o->cub_tmp, tmp, o->d_keep,
-                                             o->d_pos, (int)take, o->stream);
-            hipLaunchKernelGGL(
-                k_map_scatter, dim3(map_grid(take)), dim3(256), 0, o->stream,
-                o->d_keep, o->d_pos, o->d_vals[0],
-                c.n_out > 1 ? o->d_vals[1] : nullptr,
-                c.n_out > 2 ? o->d_vals[2] : nullptr,
-                c.n_out > 3 ? o->d_vals[3] : nullptr,
-                c.n_out > 4 ? o->d_vals[4] : nullptr,
-                c.n_out > 5 ? o->d_vals[5] : nullptr, o->d_out[0],
-                c.n_out > 1 ? o->d_out[1] : nullptr,
-                c.n_out > 2 ? o->d_out[2] : nullptr,
-                c.n_out > 3 ? o->d_out[3] : nullptr,
-                c.n_out > 4 ? o->d_out[4] : nullptr,
-                c.n_out > 5 ? o->d_out[5] : nullptr, c.n_out, take);
-            MHIP(o, hipGetLastError());
-            /* n_keep = pos[last] + keep[last] */
-            int64_t tail[2] = {0, 0};
-            MHIP(o, hipMemcpyAsync(&tail[0], o->d_pos + (take - 1), 8,
-                                   hipMemcpyDeviceToHost, o->stream));
-            MHIP(o, hipMemcpyAsync(&tail[1], o->d_keep + (take - 1), 8,
-                                   hipMemcpyDeviceToHost, o->stream));
-            MHIP(o, hipStreamSynchronize(o->stream));
-            n_keep = tail[0] + tail[1];
-            for (int i = 0; i < c.n_out; i++) src[i] = o->d_out[i];
-        }
-        int derr = 0;
-        MHIP(o, hipMemcpyAsync(&derr, o->d_err, 4, hipMemcpyDeviceToHost,
-                               o->stream));
-        MHIP(o, hipStreamSynchronize(o->stream));
-        if (derr) {
-            snprintf(o->err_msg, sizeof o->err_msg, "division by zero");
+        const int64_t *dcols[AMD_MAP_MAX_REGS], *src[AMD_MAP_MAX_OUT];
+        int64_t n_keep = 0;
+        if (o->stg.stage_chunk(o, cols, n_cols, done, take, dcols) ||
+            map_eval(o, dcols, n_cols, take, src, &n_keep))
             return 1;
-        }
-        if (n_keep) {
-            for (int i = 0; i < c.n_out; i++) {
-                out->cols[i] = realloc(out->cols[i],
-                                       (size_t)(emitted + n_keep) * 8);
-                MHIP(o, hipMemcpyAsync((int64_t *)out->cols[i] + emitted,
-                                       src[i], (size_t)n_keep * 8,
-                                       hipMemcpyDeviceToHost, o->stream));
-            }
-            MHIP(o, hipStreamSynchronize(o->stream));
-            emitted += n_keep;
-        }
+        for (int i = 0; i < c.n_out && n_keep; i++)
+            HIP_CHECK(o, hipMemcpyAsync((int64_t *)out->cols[i] + emitted,
+                                        src[i], (size_t)n_keep * 8,
+                                        hipMemcpyDeviceToHost, o->stream));
+        /* staging and d_vals are reused by the next chunk */
+        HIP_CHECK(o, hipStreamSynchronize(o->stream));
+        emitted += n_keep;
         done += take;
     }
     out->n_rows = emitted;
-    for (int i = 0; i < c.n_out; i++)
-        if (!out->cols[i]) out->cols[i] = malloc(8);
+    /* give back what the filter dropped; a shrinking realloc that fails
+     * leaves the column as it was */
+    size_t keep_bytes = (size_t)(emitted ? emitted : 1) * 8;
+    for (int i = 0; i < c.n_out && emitted < n_rows; i++)
+        if (void *p = realloc(out->cols[i], keep_bytes)) out->cols[i] = p;
     return 0;
 }
 
@@ -318,68 +276,14 @@ API int arroyo_amd_map_process_batch_device(void *h,
                                             const int64_t **d_out_cols,
                                             int64_t *n_out_rows) {
     GpuMap *o = (GpuMap *)h;
-    const AmdMapConfig &c = o->cfg;
-    if (n_cols != c.n_in_cols) {
-        snprintf(o->err_msg, sizeof o->err_msg, "expected %d cols, got %d",
-                 c.n_in_cols, n_cols);
-        return 1;
-    }
+    if (map_check_cols(o, n_cols)) return 1;
     if (n_rows > o->cap) {
         snprintf(o->err_msg, sizeof o->err_msg,
                  "device batch of %lld rows exceeds capacity %lld",
                  (long long)n_rows, (long long)o->cap);
         return 1;
     }
-    MapArgs A = {};
-    for (int cc = 0; cc < n_cols; cc++) A.cols[cc] = dcols[cc];
-    A.n_in = n_cols;
-    A.n_rows = n_rows;
-    A.cfg = c;
-    A.keep = c.filter_reg >= 0 ? o->d_keep : nullptr;
-    for (int i = 0; i < c.n_out; i++) A.vals[i] = o->d_vals[i];
-    A.err = o->d_err;
-    hipLaunchKernelGGL(k_map_eval, dim3(map_grid(n_rows)), dim3(256), 0,
-                       o->stream, A);
-    MHIP(o, hipGetLastError());
-    int64_t n_keep = n_rows;
-    if (c.filter_reg >= 0 && n_rows > 0) {
-        size_t tmp = o->cub_bytes;
-        hipcub::DeviceScan::ExclusiveSum(o->cub_tmp, tmp, o->d_keep,
-                                         o->d_pos, (int)n_rows, o->stream);
-        hipLaunchKernelGGL(
-            k_map_scatter, dim3(map_grid(n_rows)), dim3(256), 0, o->stream,
-            o->d_keep, o->d_pos, o->d_vals[0],
-            c.n_out > 1 ? o->d_vals[1] : nullptr,
-            c.n_out > 2 ? o->d_vals[2] : nullptr,
-            c.n_out > 3 ? o->d_vals[3] : nullptr,
-            c.n_out > 4 ? o->d_vals[4] : nullptr,
-            c.n_out > 5 ? o->d_vals[5] : nullptr, o->d_out[0],
-            c.n_out > 1 ? o->d_out[1] : nullptr,
-            c.n_out > 2 ? o->d_out[2] : nullptr,
-            c.n_out > 3 ? o->d_out[3] : nullptr,
-            c.n_out > 4 ? o->d_out[4] : nullptr,
-            c.n_out > 5 ? o->d_out[5] : nullptr, c.n_out, n_rows);
-        MHIP(o, hipGetLastError());
-        int64_t tail[2] = {0, 0};
-        MHIP(o, hipMemcpyAsync(&tail[0], o->d_pos + (n_rows - 1), 8,
-                               hipMemcpyDeviceToHost, o->stream));
-        MHIP(o, hipMemcpyAsync(&tail[1], o->d_keep + (n_rows - 1), 8,
-                               hipMemcpyDeviceToHost, o->stream));
-        MHIP(o, hipStreamSynchronize(o->stream));
-        n_keep = tail[0] + tail[1];
-    }
-    int derr = 0;
-    MHIP(o, hipMemcpyAsync(&derr, o->d_err, 4, hipMemcpyDeviceToHost,
-                           o->stream));
-    MHIP(o, hipStreamSynchronize(o->stream));
-    if (derr) {
-        snprintf(o->err_msg, sizeof o->err_msg, "division by zero");
-        return 1;
-    }
-    for (int i = 0; i < c.n_out; i++)
-        d_out_cols[i] = c.filter_reg >= 0 ? o->d_out[i] : o->d_vals[i];
-    *n_out_rows = n_keep;
-    return 0;
+    return map_eval(o, dcols, n_cols, n_rows, d_out_cols, n_out_rows);
 }
 
 API int arroyo_amd_map_process_batch(void *h, const int64_t *const *cols,
@@ -389,33 +293,12 @@ API int arroyo_amd_map_process_batch(void *h, const int64_t *const *cols,
     memset(out, 0, sizeof *out); /* so early-validation errors leave a
                                   * well-defined (empty) out */
     int rc = map_run(o, cols, n_cols, n_rows, out);
-    if (rc && out->cols) {
-        /* error exits (device error, HIP failure) must not leak the
-         * partially filled output the caller will never free */
-        for (int i = 0; i < out->n_cols; i++) free(out->cols[i]);
-        free(out->cols);
-        free(out->is_f64);
-        memset(out, 0, sizeof *out);
-    }
+    /* error exits (device error, HIP failure) must not leak the partially
+     * filled output the caller will never free */
+    if (rc) out_free_host(out);
     return rc;
 }
 
 API void arroyo_amd_map_destroy(void *h) {
-    GpuMap *o = (GpuMap *)h;
-    if (!o) return;
-    hipStreamSynchronize(o->stream);
-    for (int i = 0; i < o->cfg.n_out; i++) {
-        hipFree(o->d_vals[i]);
-        hipFree(o->d_out[i]);
-    }
-    hipFree(o->d_keep);
-    hipFree(o->d_pos);
-    hipFree(o->d_err);
-    hipFree(o->cub_tmp);
-    for (int c = 0; c < o->cfg.n_in_cols; c++) {
-        hipHostFree(o->stg_h[c]);
-        hipFree(o->stg_d[c]);
-    }
-    hipStreamDestroy(o->stream);
-    delete o;
+    delete (GpuMap *)h;   /* ~OpBase drains the stream first */
 }

@@ -44,21 +44,10 @@
  * the reference's session_window / global_session_window golden vectors) by
  * tests/test_session.py.
  */
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-#include "../../include/arroyo_amd_types.h"
-
-#define API extern "C" __attribute__((visibility("default")))
+#include "op_common.h"
 
 namespace sess {
 
-#define EMPTY_KEY (-1LL)
 #define SERR_TABLE_FULL 1
 #define SERR_BATCH_FULL 2
 #define SERR_SESSIONS   3
@@ -75,13 +64,6 @@ __host__ __device__ inline uint64_t enc_max(int64_t v) {
 }
 __host__ __device__ inline int64_t dec_max(uint64_t e) {
     return (int64_t)(e ^ 0x8000000000000000ULL);
-}
-
-__device__ inline uint64_t hash64(uint64_t x) {
-    x += 0x9e3779b97f4a7c15ULL;
-    x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ULL;
-    x = (x ^ (x >> 27)) * 0x94d049bb133111ebULL;
-    return x ^ (x >> 31);
 }
 
 /* aggregate state: n_aggs x 2 u64 words, zero = identity (memset-clear):
@@ -979,9 +961,7 @@ k_sess_restore_values(CdRestoreArgs R) {
 
 using namespace sess;
 
-static char g_sess_err[256];
-
-struct GpuSession {
+struct GpuSession : OpBase {
     AmdSessionConfig cfg;
     AggSpec agg;
     Store store;
@@ -996,42 +976,33 @@ struct GpuSession {
     unsigned long long *bv_cur;
     int64_t *d_out[AMD_MAX_AGGS * 2 + 4];
     unsigned long long *d_n_out;
-    int *d_err;
-    int64_t *stg_h[12], *stg_d[12];
-    int64_t stg_cap;
+    Staging stg;
     int n_in_cols, out_cols, drain_cols;
     int64_t out_cap;
     /* live-slot index flip buffers (see Store.live) */
     uint32_t *live_buf[2];
     unsigned long long *live_nbuf[2];
     int live_cur;
-    int use_live;
+    int use_live;             /* ARROYO_AMD_SESS_LIVE_IDX, default 1 */
+    /* update-launch knobs, read once at create */
+    int force_blocks;         /* ARROYO_AMD_SESS_BLOCKS: grid size,
+                                 0 = computed */
+    int use_batch;            /* ARROYO_AMD_SESS_BATCH=0: no quad-batched
+                                 path */
     int has_wm; uint64_t wm;
-    hipStream_t stream;
-    char err_msg[512];
 };
-
-#define SHIP(o, call)                                                         \
-    do {                                                                      \
-        hipError_t _e = (call);                                               \
-        if (_e != hipSuccess) {                                               \
-            snprintf((o)->err_msg, sizeof (o)->err_msg, "%s:%d hip: %s",      \
-                     __FILE__, __LINE__, hipGetErrorString(_e));              \
-            return 1;                                                         \
-        }                                                                     \
-    } while (0)
 
 API void *arroyo_amd_session_create(const AmdSessionConfig *cfg) {
     if (!cfg || cfg->n_keys < 0 || cfg->n_keys > 1 || cfg->n_value_cols < 0 ||
         cfg->n_value_cols > 8 || cfg->n_aggs < 1 ||
         cfg->n_aggs > AMD_MAX_AGGS || cfg->gap_nanos == 0) {
-        snprintf(g_sess_err, sizeof g_sess_err, "invalid session config");
+        snprintf(g_create_err, sizeof g_create_err, "invalid session config");
         return nullptr;
     }
     for (int a = 0; a < cfg->n_aggs; a++)
         if (cfg->agg_ops[a] >= AMD_AGG_MEDIAN &&
             cfg->agg_ops[a] <= AMD_AGG_MAX_RETRACT) {
-            snprintf(g_sess_err, sizeof g_sess_err,
+            snprintf(g_create_err, sizeof g_create_err,
                      "invalid session config: aggregate op %d is "
                      "updating-aggregate only", cfg->agg_ops[a]);
             return nullptr;
@@ -1040,7 +1011,7 @@ API void *arroyo_amd_session_create(const AmdSessionConfig *cfg) {
     for (int a = 0; a < cfg->n_aggs; a++)
         if (cfg->agg_ops[a] == AMD_AGG_COUNT_DISTINCT) {
             if (cd_agg >= 0 || cfg->agg_col[a] < 0) {
-                snprintf(g_sess_err, sizeof g_sess_err,
+                snprintf(g_create_err, sizeof g_create_err,
                          "at most one COUNT DISTINCT aggregate, over a "
                          "value column");
                 return nullptr;
@@ -1063,120 +1034,87 @@ API void *arroyo_amd_session_create(const AmdSessionConfig *cfg) {
     o->out_cols = cfg->n_keys + cfg->n_aggs + 3;
     o->drain_cols = cfg->n_keys + 2 * cfg->n_aggs + 2;
     if (hipSetDevice(cfg->device) != hipSuccess) {
-        snprintf(g_sess_err, sizeof g_sess_err,
+        snprintf(g_create_err, sizeof g_create_err,
                  "hipSetDevice(%d) failed: no HIP device (no CPU fallback)",
                  cfg->device);
         delete o;
         return nullptr;
     }
-    hipError_t e;
-    auto fail = [&](const char *what, hipError_t e2) {
-        snprintf(g_sess_err, sizeof g_sess_err, "%s: %s", what,
-                 hipGetErrorString(e2));
-        delete o;
-        return nullptr;
-    };
-#define SALLOC(p, bytes)                                                      \
-    if ((e = hipMalloc((void **)&(p), (bytes))) != hipSuccess)                \
-        return fail(#p, e);
     size_t C1 = (size_t)o->store.C + 1;
     size_t MS = o->store.MS, sw = 2 * (size_t)cfg->n_aggs;
     o->store.sess_w = (uint32_t)(2 + sw);
     /* pad records to a 64B multiple so the first session never straddles
      * a line */
     o->store.rec_w = (uint32_t)((MS * (2 + sw) + 7) & ~7u);
-    SALLOC(o->store.keys, C1 * 8);
-    SALLOC(o->store.ns, C1 * 4);
-    SALLOC(o->live_buf[0], C1 * 4);
-    SALLOC(o->live_buf[1], C1 * 4);
-    SALLOC(o->live_nbuf[0], 8);
-    SALLOC(o->live_nbuf[1], 8);
-    SALLOC(o->store.recs, C1 * o->store.rec_w * 8);
-    SALLOC(o->bkeys, ((size_t)o->B + 1) * 8);
-    SALLOC(o->bst, ((size_t)o->B + 1) * (2 + sw) * 8);
+    OP_ALLOC(o, o->store.keys, C1 * 8, 0xFF);
+    OP_ALLOC(o, o->store.ns, C1 * 4, 0);
+    OP_ALLOC(o, o->live_buf[0], C1 * 4);
+    OP_ALLOC(o, o->live_buf[1], C1 * 4);
+    OP_ALLOC(o, o->live_nbuf[0], 8, 0);
+    OP_ALLOC(o, o->live_nbuf[1], 8, 0);
+    OP_ALLOC(o, o->store.recs, C1 * o->store.rec_w * 8, 0);
+    OP_ALLOC(o, o->bkeys, ((size_t)o->B + 1) * 8, 0xFF);
+    OP_ALLOC(o, o->bst, ((size_t)o->B + 1) * (2 + sw) * 8, 0);
     int max_out = o->drain_cols > o->out_cols ? o->drain_cols : o->out_cols;
     for (int i = 0; i < max_out; i++)
-        SALLOC(o->d_out[i], (size_t)o->out_cap * 8);
-    SALLOC(o->d_n_out, 8);
-    SALLOC(o->d_err, 4);
+        OP_ALLOC(o, o->d_out[i], (size_t)o->out_cap * 8);
+    OP_ALLOC(o, o->d_n_out, 8);
+    OP_ALLOC(o, o->d_err, 4, 0);
     if (cd_agg >= 0) {
         o->cd.D = 1u << (cfg->log2_distinct ? cfg->log2_distinct : 10);
         o->cd.n_regions =
             1ll << (cfg->log2_cd_regions ? cfg->log2_cd_regions : 14);
         size_t words = (size_t)(o->cd.D / 64 + o->cd.D);
-        SALLOC(o->cd.regions, (size_t)o->cd.n_regions * words * 8);
-        SALLOC(o->cd.rcur, 8);
-        SALLOC(o->bv_val, (size_t)(1 << 20) * 8);
-        SALLOC(o->bv_next, (size_t)(1 << 20) * 4);
-        SALLOC(o->bv_cur, 8);
-        hipMemset(o->cd.regions, 0,
-                  (size_t)o->cd.n_regions * words * 8);
-        hipMemset(o->cd.rcur, 0, 8);
-        hipMemset(o->bv_cur, 0, 8);
+        OP_ALLOC(o, o->cd.regions, (size_t)o->cd.n_regions * words * 8, 0);
+        OP_ALLOC(o, o->cd.rcur, 8, 0);
+        OP_ALLOC(o, o->bv_val, (size_t)(1 << 20) * 8);
+        OP_ALLOC(o, o->bv_next, (size_t)(1 << 20) * 4);
+        OP_ALLOC(o, o->bv_cur, 8, 0);
     }
-#undef SALLOC
-    hipMemset(o->store.keys, 0xFF, C1 * 8);
-    hipMemset(o->store.ns, 0, C1 * 4);
-    hipMemset(o->live_nbuf[0], 0, 8);
-    hipMemset(o->live_nbuf[1], 0, 8);
     o->live_cur = 0;
     o->use_live = 1;
     if (const char *ev = getenv("ARROYO_AMD_SESS_LIVE_IDX"))
         o->use_live = atoi(ev) != 0;
+    if (const char *ev = getenv("ARROYO_AMD_SESS_BLOCKS"))
+        if (atoi(ev) > 0) o->force_blocks = atoi(ev);
+    o->use_batch = 1;
+    if (const char *ev = getenv("ARROYO_AMD_SESS_BATCH"))
+        o->use_batch = atoi(ev) != 0;
     if (o->use_live) {
         o->store.live = o->live_buf[0];
         o->store.live_n = o->live_nbuf[0];
     }
-    hipMemset(o->store.recs, 0, C1 * o->store.rec_w * 8);
-    hipMemset(o->bkeys, 0xFF, ((size_t)o->B + 1) * 8);
-    hipMemset(o->bst, 0, ((size_t)o->B + 1) * (2 + sw) * 8);
-    hipMemset(o->d_err, 0, 4);
-    hipStreamCreate(&o->stream);
-    o->stg_cap = 1 << 20;
-    for (int c = 0; c < o->n_in_cols; c++) {
-        if (hipHostMalloc((void **)&o->stg_h[c], (size_t)o->stg_cap * 8) !=
-                hipSuccess ||
-            hipMalloc((void **)&o->stg_d[c], (size_t)o->stg_cap * 8) !=
-                hipSuccess) {
-            snprintf(g_sess_err, sizeof g_sess_err,
-                     "session staging alloc failed");
-            delete o;
-            return nullptr;
-        }
-    }
+    OP_TRY(o, "hipStreamCreate", o->stream_create(&o->stream));
+    OP_TRY_MSG(o, "session staging alloc failed",
+               o->stg.alloc(o, o->n_in_cols, 1 << 20));
     return o;
 }
 
 API const char *arroyo_amd_session_last_error(void *h) {
-    return h ? ((GpuSession *)h)->err_msg : g_sess_err;
+    return h ? ((GpuSession *)h)->err_msg : g_create_err;
 }
 
-static int sess_check_err(GpuSession *o) {
-    int e = 0;
-    SHIP(o, hipMemcpyAsync(&e, o->d_err, 4, hipMemcpyDeviceToHost,
-                           o->stream));
-    SHIP(o, hipStreamSynchronize(o->stream));
-    if (!e) return 0;
-    const char *msg =
-        e == SERR_TABLE_FULL ? "session key table full; raise log2_capacity"
-        : e == SERR_BATCH_FULL
-            ? "per-batch table full; raise log2_batch_capacity"
-        : e == SERR_SESSIONS
-            ? "per-key live-session limit hit; raise max_sessions"
-        : e == SERR_OUT_CAP ? "output buffer full; raise log2_out_cap"
-        : e == SERR_CD_FULL
-            ? "per-session distinct set full; raise log2_distinct"
-        : e == SERR_CD_REGIONS
-            ? "distinct-set region pool full; raise log2_cd_regions"
-        : e == SERR_BV_POOL ? "batch value-chain pool full"
-                            : "device error";
-    snprintf(o->err_msg, sizeof o->err_msg, "%s", msg);
+static const char *sess_err_msg(int e) {
+    return e == SERR_TABLE_FULL
+               ? "session key table full; raise log2_capacity"
+           : e == SERR_BATCH_FULL
+               ? "per-batch table full; raise log2_batch_capacity"
+           : e == SERR_SESSIONS
+               ? "per-key live-session limit hit; raise max_sessions"
+           : e == SERR_OUT_CAP ? "output buffer full; raise log2_out_cap"
+           : e == SERR_CD_FULL
+               ? "per-session distinct set full; raise log2_distinct"
+           : e == SERR_CD_REGIONS
+               ? "distinct-set region pool full; raise log2_cd_regions"
+           : e == SERR_BV_POOL ? "batch value-chain pool full"
+                               : "device error";
+}
+
+static int sess_check_cols(GpuSession *o, int32_t n_cols) {
+    if (n_cols == o->n_in_cols) return 0;
+    snprintf(o->err_msg, sizeof o->err_msg, "expected %d cols, got %d",
+             o->n_in_cols, n_cols);
     return 1;
-}
-
-static int grid_for(int64_t want_threads) {
-    int64_t want = (want_threads + 255) / 256;
-    return (int)(want > 4096 ? 4096 : (want < 1 ? 1 : want));
 }
 
 /* one sub-batch whose event-time span is < gap */
@@ -1205,26 +1143,21 @@ static int sess_submit(GpuSession *o, const int64_t *const *dcols,
     }
     A.err = o->d_err;
     size_t shmem = (size_t)SESS_LDS_SLOTS * (2 + 2 * o->cfg.n_aggs) * 8;
-    int ublocks = grid_for(n_rows);
-    if (const char *ev = getenv("ARROYO_AMD_SESS_BLOCKS"))
-        if (atoi(ev) > 0) ublocks = atoi(ev);
+    int ublocks = o->force_blocks ? o->force_blocks : grid_for(n_rows, 4096);
     /* quad-batched path: keyed, no COUNT DISTINCT, 16B-aligned columns */
-    bool batch = o->cfg.n_keys == 1 && o->cd_agg < 0 && n_rows >= 4;
+    bool batch = o->use_batch && o->cfg.n_keys == 1 && o->cd_agg < 0 &&
+                 n_rows >= 4;
     for (int c = 0; c < o->n_in_cols && batch; c++)
         batch = ((uintptr_t)dcols[c] & 15) == 0;
-    if (const char *ev = getenv("ARROYO_AMD_SESS_BATCH"))
-        if (!atoi(ev)) batch = false;
     if (batch) {
         int64_t main_rows = n_rows & ~3ll;
         UpdateArgs B4 = A;
         B4.n_rows = main_rows;
-        int64_t want = (main_rows / 4 + 255) / 256;
-        int qb = (int)(want > 2048 ? 2048 : (want < 1 ? 1 : want));
-        if (const char *ev = getenv("ARROYO_AMD_SESS_BLOCKS"))
-            if (atoi(ev) > 0) qb = atoi(ev);
+        int qb = o->force_blocks ? o->force_blocks
+                                 : grid_for(main_rows / 4, 2048);
         hipLaunchKernelGGL(k_sess_update_batch, dim3(qb), dim3(256), shmem,
                            o->stream, B4);
-        SHIP(o, hipGetLastError());
+        HIP_CHECK(o, hipGetLastError());
         int64_t tail = n_rows - main_rows;
         if (tail) {
             UpdateArgs T = A;
@@ -1233,12 +1166,12 @@ static int sess_submit(GpuSession *o, const int64_t *const *dcols,
             T.n_rows = tail;
             hipLaunchKernelGGL(k_sess_update, dim3(1), dim3(64), shmem,
                                o->stream, T);
-            SHIP(o, hipGetLastError());
+            HIP_CHECK(o, hipGetLastError());
         }
     } else {
         hipLaunchKernelGGL(k_sess_update, dim3(ublocks), dim3(256),
                            shmem, o->stream, A);
-        SHIP(o, hipGetLastError());
+        HIP_CHECK(o, hipGetLastError());
     }
     MergeArgs M = {};
     M.bkeys = o->bkeys;
@@ -1253,9 +1186,9 @@ static int sess_submit(GpuSession *o, const int64_t *const *dcols,
     M.bv_next = o->bv_next;
     M.bv_cur = o->bv_cur;
     M.err = o->d_err;
-    hipLaunchKernelGGL(k_sess_merge, dim3(grid_for((int64_t)o->B + 1)),
+    hipLaunchKernelGGL(k_sess_merge, dim3(grid_for((int64_t)o->B + 1, 4096)),
                        dim3(256), 0, o->stream, M);
-    SHIP(o, hipGetLastError());
+    HIP_CHECK(o, hipGetLastError());
     return 0;
 }
 
@@ -1265,11 +1198,7 @@ API int arroyo_amd_session_process_batch_device(void *h,
                                                 int64_t n_rows,
                                                 uint64_t ts_offset) {
     GpuSession *o = (GpuSession *)h;
-    if (n_cols != o->n_in_cols) {
-        snprintf(o->err_msg, sizeof o->err_msg, "expected %d cols, got %d",
-                 o->n_in_cols, n_cols);
-        return 1;
-    }
+    if (sess_check_cols(o, n_cols)) return 1;
     /* the caller owns the guarantee that the batch's event-time span is
      * < gap on this path (bench-style streams: ms spans vs second gaps) */
     return sess_submit(o, dcols, n_rows, ts_offset);
@@ -1286,11 +1215,7 @@ API int arroyo_amd_session_process_batches_device(void *h,
                                                   int32_t reps,
                                                   uint64_t ts_offset) {
     GpuSession *o = (GpuSession *)h;
-    if (n_cols != o->n_in_cols) {
-        snprintf(o->err_msg, sizeof o->err_msg, "expected %d cols, got %d",
-                 o->n_in_cols, n_cols);
-        return 1;
-    }
+    if (sess_check_cols(o, n_cols)) return 1;
     const int64_t *cols[8];
     for (int32_t k = 0; k < reps; k++) {
         for (int c = 0; c < n_cols; c++)
@@ -1303,11 +1228,7 @@ API int arroyo_amd_session_process_batches_device(void *h,
 API int arroyo_amd_session_process_batch(void *h, const int64_t *const *cols,
                                          int32_t n_cols, int64_t n_rows) {
     GpuSession *o = (GpuSession *)h;
-    if (n_cols != o->n_in_cols) {
-        snprintf(o->err_msg, sizeof o->err_msg, "expected %d cols, got %d",
-                 o->n_in_cols, n_cols);
-        return 1;
-    }
+    if (sess_check_cols(o, n_cols)) return 1;
     if (n_rows == 0) return 0;
     const int64_t *ts = cols[n_cols - 1];
     /* bucket rows by floor(ts / (gap/2)) so each sub-batch spans < gap;
@@ -1341,18 +1262,15 @@ API int arroyo_amd_session_process_batch(void *h, const int64_t *const *cols,
         int64_t sent = 0;
         while (sent < take) {
             int64_t chunk = take - sent;
-            if (chunk > o->stg_cap) chunk = o->stg_cap;
+            if (chunk > o->stg.cap) chunk = o->stg.cap;
             const int64_t *dcols[12];
             for (int c = 0; c < o->n_in_cols; c++) {
                 for (int64_t i = 0; i < chunk; i++)
-                    o->stg_h[c][i] = cols[c][order[done + sent + i]];
-                SHIP(o, hipMemcpyAsync(o->stg_d[c], o->stg_h[c],
-                                       (size_t)chunk * 8,
-                                       hipMemcpyHostToDevice, o->stream));
-                dcols[c] = o->stg_d[c];
+                    o->stg.h[c][i] = cols[c][order[done + sent + i]];
+                if (o->stg.upload_col(o, c, chunk, dcols)) return 1;
             }
             if (sess_submit(o, dcols, chunk, 0)) return 1;
-            SHIP(o, hipStreamSynchronize(o->stream));
+            HIP_CHECK(o, hipStreamSynchronize(o->stream));
             sent += chunk;
         }
         done += take;
@@ -1363,10 +1281,10 @@ API int arroyo_amd_session_process_batch(void *h, const int64_t *const *cols,
 API int arroyo_amd_session_handle_watermark(void *h, uint64_t wm,
                                             AmdOutBatch *out) {
     GpuSession *o = (GpuSession *)h;
-    if (sess_check_err(o)) return 1;
+    if (op_check_err(o, sess_err_msg)) return 1;
     o->has_wm = 1;
     o->wm = wm;
-    SHIP(o, hipMemsetAsync(o->d_n_out, 0, 8, o->stream));
+    HIP_CHECK(o, hipMemsetAsync(o->d_n_out, 0, 8, o->stream));
     FireArgs F = {};
     F.store = o->store;
     F.gap = o->cfg.gap_nanos;
@@ -1381,7 +1299,7 @@ API int arroyo_amd_session_handle_watermark(void *h, uint64_t wm,
         /* fire over the live index, compacting survivors into the flip
          * buffer; subsequent merges append there */
         int nxt = 1 - o->live_cur;
-        SHIP(o, hipMemsetAsync(o->live_nbuf[nxt], 0, 8, o->stream));
+        HIP_CHECK(o, hipMemsetAsync(o->live_nbuf[nxt], 0, 8, o->stream));
         FireIdxArgs X = {};
         X.f = F;
         X.old_idx = o->live_buf[o->live_cur];
@@ -1390,46 +1308,36 @@ API int arroyo_amd_session_handle_watermark(void *h, uint64_t wm,
         X.new_n = o->live_nbuf[nxt];
         hipLaunchKernelGGL(k_sess_fire_idx, dim3(2048), dim3(256), 0,
                            o->stream, X);
-        SHIP(o, hipGetLastError());
+        HIP_CHECK(o, hipGetLastError());
         o->live_cur = nxt;
         o->store.live = o->live_buf[nxt];
         o->store.live_n = o->live_nbuf[nxt];
     } else {
         hipLaunchKernelGGL(k_sess_fire,
-                           dim3(grid_for((int64_t)o->store.C + 1)),
+                           dim3(grid_for((int64_t)o->store.C + 1, 4096)),
                            dim3(256), 0, o->stream, F);
-        SHIP(o, hipGetLastError());
+        HIP_CHECK(o, hipGetLastError());
     }
     unsigned long long n = 0;
-    SHIP(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
-                           o->stream));
-    SHIP(o, hipStreamSynchronize(o->stream));
-    if (sess_check_err(o)) return 1;
+    HIP_CHECK(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
+                                o->stream));
+    HIP_CHECK(o, hipStreamSynchronize(o->stream));
+    if (op_check_err(o, sess_err_msg)) return 1;
     if (out) {
-        memset(out, 0, sizeof *out);
-        out->n_rows = (int64_t)n;
-        out->n_cols = o->out_cols;
-        out->cols = (void **)calloc(o->out_cols, sizeof(void *));
-        out->is_f64 = (int32_t *)calloc(o->out_cols, sizeof(int32_t));
+        if (op_out_alloc(o, out, (int64_t)n, o->out_cols, __func__))
+            return 1;
         for (int a = 0; a < o->cfg.n_aggs; a++)
             if (o->cfg.agg_ops[a] == AMD_AGG_AVG)
                 out->is_f64[o->cfg.n_keys + a] = 1;
-        for (int i = 0; i < o->out_cols; i++) {
-            out->cols[i] = malloc((size_t)(n ? n : 1) * 8);
-            if (n)
-                SHIP(o, hipMemcpyAsync(out->cols[i], o->d_out[i],
-                                       (size_t)n * 8, hipMemcpyDeviceToHost,
-                                       o->stream));
-        }
-        SHIP(o, hipStreamSynchronize(o->stream));
+        if (out_copy_cols(o, out, o->d_out, (int64_t)n)) return 1;
     }
     return 0;
 }
 
 API int arroyo_amd_session_checkpoint_drain(void *h, AmdOutBatch *out) {
     GpuSession *o = (GpuSession *)h;
-    if (sess_check_err(o)) return 1;
-    SHIP(o, hipMemsetAsync(o->d_n_out, 0, 8, o->stream));
+    if (op_check_err(o, sess_err_msg)) return 1;
+    HIP_CHECK(o, hipMemsetAsync(o->d_n_out, 0, 8, o->stream));
     DrainArgs D = {};
     D.store = o->store;
     for (int i = 0; i < o->drain_cols; i++) D.out[i] = o->d_out[i];
@@ -1439,27 +1347,17 @@ API int arroyo_amd_session_checkpoint_drain(void *h, AmdOutBatch *out) {
     D.n_aggs = o->cfg.n_aggs;
     D.err = o->d_err;
     hipLaunchKernelGGL(k_sess_drain,
-                       dim3(grid_for((int64_t)o->store.C + 1)), dim3(256), 0,
+                       dim3(grid_for((int64_t)o->store.C + 1, 4096)),
+                       dim3(256), 0,
                        o->stream, D);
-    SHIP(o, hipGetLastError());
+    HIP_CHECK(o, hipGetLastError());
     unsigned long long n = 0;
-    SHIP(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
-                           o->stream));
-    SHIP(o, hipStreamSynchronize(o->stream));
-    if (sess_check_err(o)) return 1;
-    memset(out, 0, sizeof *out);
-    out->n_rows = (int64_t)n;
-    out->n_cols = o->drain_cols;
-    out->cols = (void **)calloc(o->drain_cols, sizeof(void *));
-    out->is_f64 = (int32_t *)calloc(o->drain_cols, sizeof(int32_t));
-    for (int i = 0; i < o->drain_cols; i++) {
-        out->cols[i] = malloc((size_t)(n ? n : 1) * 8);
-        if (n)
-            SHIP(o, hipMemcpyAsync(out->cols[i], o->d_out[i], (size_t)n * 8,
-                                   hipMemcpyDeviceToHost, o->stream));
-    }
-    SHIP(o, hipStreamSynchronize(o->stream));
-    return 0;
+    HIP_CHECK(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
+                                o->stream));
+    HIP_CHECK(o, hipStreamSynchronize(o->stream));
+    if (op_check_err(o, sess_err_msg)) return 1;
+    return op_out_alloc(o, out, (int64_t)n, o->drain_cols, __func__) ||
+           out_copy_cols(o, out, o->d_out, (int64_t)n);
 }
 
 API int arroyo_amd_session_restore(void *h, const int64_t *const *cols,
@@ -1503,23 +1401,14 @@ API int arroyo_amd_session_restore(void *h, const int64_t *const *cols,
     }
     off.push_back(n_rows);
     int64_t n_groups = (int64_t)off.size() - 1;
+    DevScratch tmp;
     int64_t *d_keys, *d_start, *d_end, *d_off;
     uint64_t *d_st;
-    SHIP(o, hipMalloc((void **)&d_keys, (size_t)n_rows * 8));
-    SHIP(o, hipMalloc((void **)&d_start, (size_t)n_rows * 8));
-    SHIP(o, hipMalloc((void **)&d_end, (size_t)n_rows * 8));
-    SHIP(o, hipMalloc((void **)&d_st, (size_t)n_rows * sw * 8));
-    SHIP(o, hipMalloc((void **)&d_off, (size_t)(n_groups + 1) * 8));
-    SHIP(o, hipMemcpy(d_keys, h_keys.data(), (size_t)n_rows * 8,
-                      hipMemcpyHostToDevice));
-    SHIP(o, hipMemcpy(d_start, h_start.data(), (size_t)n_rows * 8,
-                      hipMemcpyHostToDevice));
-    SHIP(o, hipMemcpy(d_end, h_end.data(), (size_t)n_rows * 8,
-                      hipMemcpyHostToDevice));
-    SHIP(o, hipMemcpy(d_st, h_st.data(), (size_t)n_rows * sw * 8,
-                      hipMemcpyHostToDevice));
-    SHIP(o, hipMemcpy(d_off, off.data(), (size_t)(n_groups + 1) * 8,
-                      hipMemcpyHostToDevice));
+    HIP_CHECK(o, tmp.upload(d_keys, h_keys.data(), h_keys.size()));
+    HIP_CHECK(o, tmp.upload(d_start, h_start.data(), h_start.size()));
+    HIP_CHECK(o, tmp.upload(d_end, h_end.data(), h_end.size()));
+    HIP_CHECK(o, tmp.upload(d_st, h_st.data(), h_st.size()));
+    HIP_CHECK(o, tmp.upload(d_off, off.data(), off.size()));
     RestoreArgs R = {};
     R.keys = d_keys;
     R.st = d_st;
@@ -1534,31 +1423,20 @@ API int arroyo_amd_session_restore(void *h, const int64_t *const *cols,
     R.cd_agg = o->cd_agg;
     R.cd = o->cd;
     R.err = o->d_err;
-    hipLaunchKernelGGL(k_sess_restore, dim3(grid_for(n_groups)), dim3(256),
+    hipLaunchKernelGGL(k_sess_restore, dim3(grid_for(n_groups, 4096)),
+                       dim3(256),
                        0, o->stream, R);
-    SHIP(o, hipGetLastError());
-    SHIP(o, hipStreamSynchronize(o->stream));
-    hipFree(d_keys);
-    hipFree(d_start);
-    hipFree(d_end);
-    hipFree(d_st);
-    hipFree(d_off);
-    return sess_check_err(o);
+    HIP_CHECK(o, hipGetLastError());
+    HIP_CHECK(o, hipStreamSynchronize(o->stream));
+    return op_check_err(o, sess_err_msg);
 }
 
 API int arroyo_amd_session_drain_values(void *h, AmdOutBatch *out) {
     GpuSession *o = (GpuSession *)h;
-    if (sess_check_err(o)) return 1;
+    if (op_check_err(o, sess_err_msg)) return 1;
     int ncols = o->cfg.n_keys + 2;
-    memset(out, 0, sizeof *out);
-    out->n_cols = ncols;
-    out->cols = (void **)calloc(ncols, sizeof(void *));
-    out->is_f64 = (int32_t *)calloc(ncols, sizeof(int32_t));
-    if (o->cd_agg < 0) {
-        for (int i = 0; i < ncols; i++) out->cols[i] = malloc(8);
-        return 0;
-    }
-    SHIP(o, hipMemsetAsync(o->d_n_out, 0, 8, o->stream));
+    if (o->cd_agg < 0) return op_out_alloc(o, out, 0, ncols, __func__);
+    HIP_CHECK(o, hipMemsetAsync(o->d_n_out, 0, 8, o->stream));
     CdDrainArgs D = {};
     D.store = o->store;
     D.agg = o->agg;
@@ -1570,23 +1448,17 @@ API int arroyo_amd_session_drain_values(void *h, AmdOutBatch *out) {
     D.out_cap = o->out_cap;
     D.err = o->d_err;
     hipLaunchKernelGGL(k_sess_drain_values,
-                       dim3(grid_for((int64_t)o->store.C + 1)), dim3(256), 0,
+                       dim3(grid_for((int64_t)o->store.C + 1, 4096)),
+                       dim3(256), 0,
                        o->stream, D);
-    SHIP(o, hipGetLastError());
+    HIP_CHECK(o, hipGetLastError());
     unsigned long long n = 0;
-    SHIP(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
-                           o->stream));
-    SHIP(o, hipStreamSynchronize(o->stream));
-    if (sess_check_err(o)) return 1;
-    out->n_rows = (int64_t)n;
-    for (int i = 0; i < ncols; i++) {
-        out->cols[i] = malloc((size_t)(n ? n : 1) * 8);
-        if (n)
-            SHIP(o, hipMemcpyAsync(out->cols[i], o->d_out[i], (size_t)n * 8,
-                                   hipMemcpyDeviceToHost, o->stream));
-    }
-    SHIP(o, hipStreamSynchronize(o->stream));
-    return 0;
+    HIP_CHECK(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
+                                o->stream));
+    HIP_CHECK(o, hipStreamSynchronize(o->stream));
+    if (op_check_err(o, sess_err_msg)) return 1;
+    return op_out_alloc(o, out, (int64_t)n, ncols, __func__) ||
+           out_copy_cols(o, out, o->d_out, (int64_t)n);
 }
 
 API int arroyo_amd_session_restore_values(void *h,
@@ -1621,19 +1493,12 @@ API int arroyo_amd_session_restore_values(void *h,
     }
     off.push_back(n_rows);
     int64_t n_groups = (int64_t)off.size() - 1;
+    DevScratch tmp;
     int64_t *d_keys, *d_start, *d_val, *d_off;
-    SHIP(o, hipMalloc((void **)&d_keys, (size_t)n_rows * 8));
-    SHIP(o, hipMalloc((void **)&d_start, (size_t)n_rows * 8));
-    SHIP(o, hipMalloc((void **)&d_val, (size_t)n_rows * 8));
-    SHIP(o, hipMalloc((void **)&d_off, (size_t)(n_groups + 1) * 8));
-    SHIP(o, hipMemcpy(d_keys, h_keys.data(), (size_t)n_rows * 8,
-                      hipMemcpyHostToDevice));
-    SHIP(o, hipMemcpy(d_start, h_start.data(), (size_t)n_rows * 8,
-                      hipMemcpyHostToDevice));
-    SHIP(o, hipMemcpy(d_val, h_val.data(), (size_t)n_rows * 8,
-                      hipMemcpyHostToDevice));
-    SHIP(o, hipMemcpy(d_off, off.data(), (size_t)(n_groups + 1) * 8,
-                      hipMemcpyHostToDevice));
+    HIP_CHECK(o, tmp.upload(d_keys, h_keys.data(), h_keys.size()));
+    HIP_CHECK(o, tmp.upload(d_start, h_start.data(), h_start.size()));
+    HIP_CHECK(o, tmp.upload(d_val, h_val.data(), h_val.size()));
+    HIP_CHECK(o, tmp.upload(d_off, off.data(), off.size()));
     CdRestoreArgs R = {};
     R.keys = d_keys;
     R.start = d_start;
@@ -1646,45 +1511,13 @@ API int arroyo_amd_session_restore_values(void *h,
     R.n_keys = o->cfg.n_keys;
     R.cd = o->cd;
     R.err = o->d_err;
-    hipLaunchKernelGGL(k_sess_restore_values, dim3(grid_for(n_groups)),
+    hipLaunchKernelGGL(k_sess_restore_values, dim3(grid_for(n_groups, 4096)),
                        dim3(256), 0, o->stream, R);
-    SHIP(o, hipGetLastError());
-    SHIP(o, hipStreamSynchronize(o->stream));
-    hipFree(d_keys);
-    hipFree(d_start);
-    hipFree(d_val);
-    hipFree(d_off);
-    return sess_check_err(o);
+    HIP_CHECK(o, hipGetLastError());
+    HIP_CHECK(o, hipStreamSynchronize(o->stream));
+    return op_check_err(o, sess_err_msg);
 }
 
 API void arroyo_amd_session_destroy(void *h) {
-    GpuSession *o = (GpuSession *)h;
-    if (!o) return;
-    hipStreamSynchronize(o->stream);
-    hipFree(o->store.keys);
-    hipFree(o->store.ns);
-    hipFree(o->live_buf[0]);
-    hipFree(o->live_buf[1]);
-    hipFree(o->live_nbuf[0]);
-    hipFree(o->live_nbuf[1]);
-    hipFree(o->store.recs);
-    hipFree(o->bkeys);
-    hipFree(o->bst);
-    int max_out = o->drain_cols > o->out_cols ? o->drain_cols : o->out_cols;
-    for (int i = 0; i < max_out; i++) hipFree(o->d_out[i]);
-    hipFree(o->d_n_out);
-    hipFree(o->d_err);
-    if (o->cd_agg >= 0) {
-        hipFree(o->cd.regions);
-        hipFree(o->cd.rcur);
-        hipFree(o->bv_val);
-        hipFree(o->bv_next);
-        hipFree(o->bv_cur);
-    }
-    for (int c = 0; c < o->n_in_cols; c++) {
-        hipHostFree(o->stg_h[c]);
-        hipFree(o->stg_d[c]);
-    }
-    hipStreamDestroy(o->stream);
-    delete o;
+    delete (GpuSession *)h;   /* ~OpBase drains the stream first */
 }

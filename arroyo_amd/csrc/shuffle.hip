@@ -34,17 +34,11 @@
  * The two Utf8 kernels return at once when the error word is set, so a
  * malformed offsets array never leads to a dereference of `data`.
  */
-#include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
 #include <climits>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 
-#include "../../include/arroyo_amd_types.h"
-
-#define API extern "C" __attribute__((visibility("default")))
+#include "op_common.h"
 
 namespace shuf {
 
@@ -74,17 +68,10 @@ struct ColPtrs {
     int64_t *out[AMD_SHUF_MAX_COLS];
 };
 
-/* the splitmix64 finaliser of arroyo_amd_partition */
-__device__ inline uint64_t hash64(uint64_t x) {
-    x += 0x9e3779b97f4a7c15ULL;
-    x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ULL;
-    x = (x ^ (x >> 27)) * 0x94d049bb133111ebULL;
-    return x ^ (x >> 31);
-}
-
 /* range == 0 stands for n_parts == 1 */
 __device__ inline uint32_t owner_of(int64_t key, int key_mode, uint64_t range) {
     if (range == 0) return 0;
+    /* hash64: the splitmix64 finaliser of arroyo_amd_partition */
     const uint64_t h =
         key_mode == AMD_SHUF_KEY_HASH ? (uint64_t)key : hash64((uint64_t)key);
     return (uint32_t)(h / range);
@@ -338,9 +325,7 @@ __global__ void k_shuf_zero_offsets(int32_t *out_off, int n_parts) {
 
 using namespace shuf;
 
-static char g_shuffle_err[256];
-
-struct GpuShuffle {
+struct GpuShuffle : OpBase {
     AmdShuffleConfig cfg;
     int max_blocks;
     int64_t *out_cols[AMD_SHUF_MAX_COLS];
@@ -356,50 +341,12 @@ struct GpuShuffle {
     uint8_t *dst_data;
     Starts *d_starts; /* d_starts->err is the device error word */
     Starts *h_starts; /* pinned */
-    hipStream_t stream;
     int32_t copy_threshold;
     /* opt-in per-kernel timing (arroyo_amd_shuffle_profile) */
     int prof_on;
     hipEvent_t ev[AMD_SHUF_N_KERNELS + 1];
     double last_ms[AMD_SHUF_N_KERNELS];
-    char err_msg[512];
 };
-
-#define SHIP(o, call)                                                         \
-    do {                                                                      \
-        hipError_t _e = (call);                                               \
-        if (_e != hipSuccess) {                                               \
-            snprintf((o)->err_msg, sizeof (o)->err_msg, "%s:%d hip: %s",      \
-                     __FILE__, __LINE__, hipGetErrorString(_e));              \
-            return 1;                                                         \
-        }                                                                     \
-    } while (0)
-
-static void shuf_release(GpuShuffle *o) {
-    for (int c = 0; c < AMD_SHUF_MAX_COLS; c++) hipFree(o->out_cols[c]);
-    hipFree(o->owner);
-    hipFree(o->hist_rows);
-    hipFree(o->hist_bytes);
-    hipFree(o->base_rows);
-    hipFree(o->base_bytes);
-    hipFree(o->len_dst);
-    hipFree(o->src_dst);
-    hipFree(o->pos_dst);
-    hipFree(o->out_off);
-    hipFree(o->out_data);
-    hipFree(o->d_starts);
-    if (o->h_starts) hipHostFree(o->h_starts);
-    for (int i = 0; i <= AMD_SHUF_N_KERNELS; i++)
-        if (o->ev[i]) hipEventDestroy(o->ev[i]);
-    if (o->stream) hipStreamDestroy(o->stream);
-    delete o;
-}
-
-template <typename P>
-static hipError_t shuf_alloc(hipError_t e, P **buf, size_t bytes) {
-    if (e != hipSuccess) return e;
-    return hipMalloc((void **)buf, bytes ? bytes : 1);
-}
 
 static void shuf_own_output(GpuShuffle *o) {
     for (int c = 0; c < AMD_SHUF_MAX_COLS; c++) o->dst_cols[c] = o->out_cols[c];
@@ -415,7 +362,7 @@ API void *arroyo_amd_shuffle_create(const AmdShuffleConfig *cfg) {
          cfg->key_mode != AMD_SHUF_KEY_HASH) ||
         cfg->max_rows < 1 || cfg->max_rows > AMD_SHUF_MAX_ROWS ||
         (cfg->has_utf8 && (cfg->max_bytes < 0 || cfg->max_bytes > INT32_MAX))) {
-        snprintf(g_shuffle_err, sizeof g_shuffle_err,
+        snprintf(g_create_err, sizeof g_create_err,
                  "invalid shuffle config (n_parts 1..%d, n_cols 1..%d, "
                  "key_col < n_cols, key_mode 0/1, max_rows 1..%lld, "
                  "max_bytes 0..INT32_MAX)",
@@ -424,7 +371,7 @@ API void *arroyo_amd_shuffle_create(const AmdShuffleConfig *cfg) {
         return nullptr;
     }
     if (hipSetDevice(cfg->device) != hipSuccess) {
-        snprintf(g_shuffle_err, sizeof g_shuffle_err,
+        snprintf(g_create_err, sizeof g_create_err,
                  "hipSetDevice(%d) failed: no HIP device (no CPU fallback)",
                  cfg->device);
         return nullptr;
@@ -436,38 +383,33 @@ API void *arroyo_amd_shuffle_create(const AmdShuffleConfig *cfg) {
     o->max_blocks = (int)((cfg->max_rows + SHUF_TILE - 1) / SHUF_TILE);
     const size_t rows = (size_t)cfg->max_rows;
     const size_t runs = (size_t)cfg->n_parts * o->max_blocks;
-    hipError_t e = hipSuccess;
     for (int c = 0; c < cfg->n_cols; c++)
-        e = shuf_alloc(e, &o->out_cols[c], rows * 8);
-    e = shuf_alloc(e, &o->owner, rows);
-    e = shuf_alloc(e, &o->hist_rows, runs * 4);
-    e = shuf_alloc(e, &o->base_rows, runs * 4);
-    e = shuf_alloc(e, &o->d_starts, sizeof(Starts));
+        OP_TRY(o, "shuffle alloc", o->dev_alloc(o->out_cols[c], rows * 8));
+    OP_TRY(o, "shuffle alloc", o->dev_alloc(o->owner, rows));
+    OP_TRY(o, "shuffle alloc", o->dev_alloc(o->hist_rows, runs * 4));
+    OP_TRY(o, "shuffle alloc", o->dev_alloc(o->base_rows, runs * 4));
+    OP_TRY(o, "shuffle alloc", o->dev_alloc(o->d_starts, sizeof(Starts)));
     if (o->cfg.has_utf8) {
-        e = shuf_alloc(e, &o->hist_bytes, runs * 4);
-        e = shuf_alloc(e, &o->base_bytes, runs * 4);
-        e = shuf_alloc(e, &o->len_dst, rows * 4);
-        e = shuf_alloc(e, &o->src_dst, rows * 4);
-        e = shuf_alloc(e, &o->pos_dst, rows * 4);
-        e = shuf_alloc(e, &o->out_off, (rows + cfg->n_parts) * 4);
-        e = shuf_alloc(e, &o->out_data, (size_t)cfg->max_bytes);
+        OP_TRY(o, "shuffle alloc", o->dev_alloc(o->hist_bytes, runs * 4));
+        OP_TRY(o, "shuffle alloc", o->dev_alloc(o->base_bytes, runs * 4));
+        OP_TRY(o, "shuffle alloc", o->dev_alloc(o->len_dst, rows * 4));
+        OP_TRY(o, "shuffle alloc", o->dev_alloc(o->src_dst, rows * 4));
+        OP_TRY(o, "shuffle alloc", o->dev_alloc(o->pos_dst, rows * 4));
+        OP_TRY(o, "shuffle alloc",
+               o->dev_alloc(o->out_off, (rows + cfg->n_parts) * 4));
+        /* max_bytes 0 still gets an address */
+        OP_TRY(o, "shuffle alloc",
+               o->dev_alloc(o->out_data,
+                            cfg->max_bytes ? (size_t)cfg->max_bytes : 1));
     }
-    if (e == hipSuccess)
-        e = hipHostMalloc((void **)&o->h_starts, sizeof(Starts),
-                          hipHostMallocDefault);
-    if (e == hipSuccess) e = hipStreamCreate(&o->stream);
-    if (e != hipSuccess) {
-        snprintf(g_shuffle_err, sizeof g_shuffle_err, "shuffle alloc: %s",
-                 hipGetErrorString(e));
-        shuf_release(o);
-        return nullptr;
-    }
+    OP_TRY(o, "shuffle alloc", o->pinned_alloc(o->h_starts, sizeof(Starts)));
+    OP_TRY(o, "shuffle alloc", o->stream_create(&o->stream));
     shuf_own_output(o);
     return o;
 }
 
 API const char *arroyo_amd_shuffle_last_error(void *h) {
-    return h ? ((GpuShuffle *)h)->err_msg : g_shuffle_err;
+    return h ? ((GpuShuffle *)h)->err_msg : g_create_err;
 }
 
 API int arroyo_amd_shuffle_bind_output(void *h, int64_t *const *d_out_cols,
@@ -503,9 +445,9 @@ API int arroyo_amd_shuffle_profile(void *h, int enable,
                                    double *last_kernel_ms) {
     GpuShuffle *o = (GpuShuffle *)h;
     if (enable > 0 && !o->ev[0]) {
-        SHIP(o, hipSetDevice(o->cfg.device));
+        HIP_CHECK(o, hipSetDevice(o->cfg.device));
         for (int i = 0; i <= AMD_SHUF_N_KERNELS; i++)
-            SHIP(o, hipEventCreate(&o->ev[i]));
+            HIP_CHECK(o, o->event_create(&o->ev[i]));
     }
     if (enable >= 0) o->prof_on = enable > 0;
     if (copy_threshold >= 0) o->copy_threshold = copy_threshold;
@@ -566,33 +508,33 @@ API int arroyo_amd_shuffle_partition_device(void *h,
         if (cfg.has_utf8) {
             hipLaunchKernelGGL(k_shuf_zero_offsets, dim3(1), dim3(64), 0,
                                o->stream, o->dst_off, cfg.n_parts);
-            SHIP(o, hipGetLastError());
-            SHIP(o, hipStreamSynchronize(o->stream));
+            HIP_CHECK(o, hipGetLastError());
+            HIP_CHECK(o, hipStreamSynchronize(o->stream));
         }
         return 0;
     }
     const int nb = (int)((n_rows + SHUF_TILE - 1) / SHUF_TILE);
     int *d_err = (int *)&o->d_starts->err;
     hipEvent_t *ev = o->prof_on ? o->ev : nullptr;
-    SHIP(o, hipMemsetAsync(&o->d_starts->err, 0, 8, o->stream));
-    if (ev) SHIP(o, hipEventRecord(ev[0], o->stream));
+    HIP_CHECK(o, hipMemsetAsync(&o->d_starts->err, 0, 8, o->stream));
+    if (ev) HIP_CHECK(o, hipEventRecord(ev[0], o->stream));
     hipLaunchKernelGGL(k_shuf_count, dim3(nb), dim3(SHUF_BLOCK), 0, o->stream,
                        C.in[cfg.key_col], off, n_rows, cfg.n_parts,
                        cfg.key_mode, o->owner, o->hist_rows, o->hist_bytes,
                        nb, d_err);
-    if (ev) SHIP(o, hipEventRecord(ev[1], o->stream));
+    if (ev) HIP_CHECK(o, hipEventRecord(ev[1], o->stream));
     hipLaunchKernelGGL(k_shuf_scan, dim3(1), dim3(SHUF_SCAN_THREADS), 0,
                        o->stream, (const uint32_t *)o->hist_rows,
                        (const uint32_t *)o->hist_bytes, o->base_rows,
                        o->base_bytes, cfg.n_parts, nb, cfg.has_utf8,
                        cfg.max_bytes, o->d_starts, d_err);
-    if (ev) SHIP(o, hipEventRecord(ev[2], o->stream));
+    if (ev) HIP_CHECK(o, hipEventRecord(ev[2], o->stream));
     hipLaunchKernelGGL(k_shuf_scatter, dim3(nb), dim3(SHUF_BLOCK), 0,
                        o->stream, C, cfg.n_cols, off, n_rows, cfg.n_parts,
                        (const uint8_t *)o->owner,
                        (const uint32_t *)o->base_rows, nb, o->len_dst,
                        o->src_dst);
-    if (ev) SHIP(o, hipEventRecord(ev[3], o->stream));
+    if (ev) HIP_CHECK(o, hipEventRecord(ev[3], o->stream));
     if (off) {
         const int64_t runs = (int64_t)cfg.n_parts * nb;
         hipLaunchKernelGGL(k_shuf_utf8_offsets,
@@ -604,7 +546,7 @@ API int arroyo_amd_shuffle_partition_device(void *h,
                            (const int32_t *)o->len_dst,
                            (const Starts *)o->d_starts, o->dst_off,
                            o->pos_dst, (const int *)d_err);
-        if (ev) SHIP(o, hipEventRecord(ev[4], o->stream));
+        if (ev) HIP_CHECK(o, hipEventRecord(ev[4], o->stream));
         hipLaunchKernelGGL(k_shuf_utf8_copy,
                            dim3(shuf_grid((n_rows + SHUF_BLOCK - 1) / SHUF_BLOCK)),
                            dim3(SHUF_BLOCK), 0, o->stream, d_data,
@@ -613,17 +555,18 @@ API int arroyo_amd_shuffle_partition_device(void *h,
                            (const int32_t *)o->pos_dst, n_rows,
                            o->copy_threshold, o->dst_data,
                            (const int *)d_err);
-        if (ev) SHIP(o, hipEventRecord(ev[5], o->stream));
+        if (ev) HIP_CHECK(o, hipEventRecord(ev[5], o->stream));
     }
-    SHIP(o, hipGetLastError());
-    SHIP(o, hipMemcpyAsync(o->h_starts, o->d_starts, sizeof(Starts),
-                           hipMemcpyDeviceToHost, o->stream));
-    SHIP(o, hipStreamSynchronize(o->stream));
+    HIP_CHECK(o, hipGetLastError());
+    HIP_CHECK(o, hipMemcpyAsync(o->h_starts, o->d_starts, sizeof(Starts),
+                               hipMemcpyDeviceToHost, o->stream));
+    HIP_CHECK(o, hipStreamSynchronize(o->stream));
     if (ev) {
         const int n_ev = off ? AMD_SHUF_N_KERNELS : 3;
         for (int i = 0; i < AMD_SHUF_N_KERNELS; i++) {
             float ms = 0.f;
-            if (i < n_ev) SHIP(o, hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+            if (i < n_ev)
+                HIP_CHECK(o, hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
             o->last_ms[i] = ms;
         }
     }
@@ -648,8 +591,5 @@ API int arroyo_amd_shuffle_partition_device(void *h,
 }
 
 API void arroyo_amd_shuffle_destroy(void *h) {
-    GpuShuffle *o = (GpuShuffle *)h;
-    if (!o) return;
-    hipStreamSynchronize(o->stream);
-    shuf_release(o);
+    delete (GpuShuffle *)h;   /* ~OpBase drains the stream first */
 }

@@ -37,17 +37,11 @@
  * bounded by the table capacity or the string length and ends in an error
  * code.
  */
-#include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
 #include <climits>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 
-#include "../../include/arroyo_amd_types.h"
-
-#define API extern "C" __attribute__((visibility("default")))
+#include "op_common.h"
 
 namespace strkey {
 
@@ -372,9 +366,7 @@ k_strkey_restore_verify(Table T, const int64_t *ids, const int32_t *off,
 
 using namespace strkey;
 
-static char g_strkey_err[256];
-
-struct GpuStrKey {
+struct GpuStrKey : OpBase {
     AmdStrKeyConfig cfg;
     Table T;
     uint64_t cap, max_occ;
@@ -391,28 +383,11 @@ struct GpuStrKey {
     int64_t ids_cap;
     uint64_t *d_hashes;
     int64_t hashes_cap;
-    hipStream_t stream;
     /* opt-in timing of the probe kernel (arroyo_amd_strkey_profile) */
     int prof_on;
     hipEvent_t ev0, ev1;
     double last_probe_ms;
-    char err_msg[512];
 };
-
-#define SHIP(o, call)                                                         \
-    do {                                                                      \
-        hipError_t _e = (call);                                               \
-        if (_e != hipSuccess) {                                               \
-            snprintf((o)->err_msg, sizeof (o)->err_msg, "%s:%d hip: %s",      \
-                     __FILE__, __LINE__, hipGetErrorString(_e));              \
-            return 1;                                                         \
-        }                                                                     \
-    } while (0)
-
-static int sk_grid(int64_t want) {
-    int64_t w = (want + 255) / 256;
-    return (int)(w > 2048 ? 2048 : (w < 1 ? 1 : w));
-}
 
 template <typename P>
 static int sk_grow(GpuStrKey *o, P **buf, int64_t *cap, int64_t want,
@@ -420,43 +395,26 @@ static int sk_grow(GpuStrKey *o, P **buf, int64_t *cap, int64_t want,
     if (want <= *cap) return 0;
     /* allocations belong on the handle's device, whatever the caller's
      * current one is */
-    SHIP(o, hipSetDevice(o->cfg.device));
+    HIP_CHECK(o, hipSetDevice(o->cfg.device));
     int64_t n = *cap ? *cap : 1024;
     while (n < want) n *= 2;
-    if (*buf) SHIP(o, hipFree(*buf));
-    *buf = nullptr;
+    o->release(*buf);
     *cap = 0;
-    SHIP(o, hipMalloc((void **)buf, (size_t)n * elem));
+    HIP_CHECK(o, o->dev_alloc(*buf, (size_t)n * elem));
     *cap = n;
     return 0;
-}
-
-static void sk_release(GpuStrKey *o) {
-    hipFree(o->T.slots);
-    hipFree(o->T.ent);
-    hipFree(o->T.arena);
-    hipFree(o->T.ctr);
-    hipFree(o->d_win);
-    hipFree(o->d_off);
-    hipFree(o->d_data);
-    hipFree(o->d_ids);
-    hipFree(o->d_hashes);
-    if (o->ev0) hipEventDestroy(o->ev0);
-    if (o->ev1) hipEventDestroy(o->ev1);
-    if (o->stream) hipStreamDestroy(o->stream);
-    delete o;
 }
 
 API void *arroyo_amd_strkey_create(const AmdStrKeyConfig *cfg) {
     if (!cfg || cfg->log2_capacity < 1 || cfg->log2_capacity > 30 ||
         cfg->arena_bytes < 1 || cfg->hash_bits < 0 || cfg->hash_bits > 63) {
-        snprintf(g_strkey_err, sizeof g_strkey_err,
+        snprintf(g_create_err, sizeof g_create_err,
                  "invalid strkey config (log2_capacity 1..30, arena_bytes "
                  ">= 1, hash_bits 0..63)");
         return nullptr;
     }
     if (hipSetDevice(cfg->device) != hipSuccess) {
-        snprintf(g_strkey_err, sizeof g_strkey_err,
+        snprintf(g_create_err, sizeof g_create_err,
                  "hipSetDevice(%d) failed: no HIP device (no CPU fallback)",
                  cfg->device);
         return nullptr;
@@ -469,32 +427,24 @@ API void *arroyo_amd_strkey_create(const AmdStrKeyConfig *cfg) {
     o->T.mask = o->cap - 1;
     o->T.hash_mask = cfg->hash_bits ? (1ull << cfg->hash_bits) - 1 : ~0ull;
     o->T.arena_bytes = cfg->arena_bytes;
-    hipError_t e = hipMalloc((void **)&o->T.slots, o->cap * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&o->T.ent, o->cap * sizeof(Ent));
-    if (e == hipSuccess)
-        e = hipMalloc((void **)&o->T.arena, (size_t)cfg->arena_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&o->T.ctr, sizeof(Ctr));
-    if (e == hipSuccess) e = hipMemset(o->T.slots, 0, o->cap * 8);
-    if (e == hipSuccess) e = hipMemset(o->T.ctr, 0, sizeof(Ctr));
-    if (e == hipSuccess) e = hipStreamCreate(&o->stream);
-    if (e != hipSuccess) {
-        snprintf(g_strkey_err, sizeof g_strkey_err, "strkey alloc: %s",
-                 hipGetErrorString(e));
-        sk_release(o);
-        return nullptr;
-    }
+    OP_TRY(o, "strkey alloc", o->dev_alloc(o->T.slots, o->cap * 8, 0));
+    OP_TRY(o, "strkey alloc", o->dev_alloc(o->T.ent, o->cap * sizeof(Ent)));
+    OP_TRY(o, "strkey alloc",
+           o->dev_alloc(o->T.arena, (size_t)cfg->arena_bytes));
+    OP_TRY(o, "strkey alloc", o->dev_alloc(o->T.ctr, sizeof(Ctr), 0));
+    OP_TRY(o, "strkey alloc", o->stream_create(&o->stream));
     return o;
 }
 
 API const char *arroyo_amd_strkey_last_error(void *h) {
-    return h ? ((GpuStrKey *)h)->err_msg : g_strkey_err;
+    return h ? ((GpuStrKey *)h)->err_msg : g_create_err;
 }
 
 /* read the counters back (synchronises the stream) and refresh the mirrors */
 static int sk_sync_counters(GpuStrKey *o, Ctr *c) {
-    SHIP(o, hipMemcpyAsync(c, o->T.ctr, sizeof(Ctr), hipMemcpyDeviceToHost,
-                           o->stream));
-    SHIP(o, hipStreamSynchronize(o->stream));
+    HIP_CHECK(o, hipMemcpyAsync(c, o->T.ctr, sizeof(Ctr), hipMemcpyDeviceToHost,
+                               o->stream));
+    HIP_CHECK(o, hipStreamSynchronize(o->stream));
     o->n_live = c->n_live;
     o->occupied = c->occupied;
     o->arena_used = c->arena_used;
@@ -548,24 +498,24 @@ static int sk_encode_device(GpuStrKey *o, const int32_t *d_off,
     }
     if (n_rows == 0) return 0;
     if (sk_grow(o, &o->d_win, &o->win_cap, n_rows, sizeof(unsigned))) return 1;
-    SHIP(o, hipMemsetAsync(o->T.ctr, 0, 8, o->stream));
-    const int grid = sk_grid(n_rows);
+    HIP_CHECK(o, hipMemsetAsync(o->T.ctr, 0, 8, o->stream));
+    const int grid = grid_for(n_rows, 2048);
     hipLaunchKernelGGL(k_strkey_check_offsets, dim3(grid), dim3(256), 0,
                        o->stream, d_off, n_rows, o->T.ctr);
-    if (o->prof_on) SHIP(o, hipEventRecord(o->ev0, o->stream));
+    if (o->prof_on) HIP_CHECK(o, hipEventRecord(o->ev0, o->stream));
     hipLaunchKernelGGL(k_strkey_probe, dim3(grid), dim3(256), 0, o->stream,
                        o->T, d_off, d_data, bias, n_rows, d_ids, d_hashes,
                        o->d_win);
-    if (o->prof_on) SHIP(o, hipEventRecord(o->ev1, o->stream));
+    if (o->prof_on) HIP_CHECK(o, hipEventRecord(o->ev1, o->stream));
     hipLaunchKernelGGL(k_strkey_publish, dim3(256), dim3(256), 0, o->stream,
                        o->T, d_off, d_data, bias, (const int64_t *)d_ids,
                        (const unsigned *)o->d_win, o->occupied, o->max_occ);
-    SHIP(o, hipGetLastError());
+    HIP_CHECK(o, hipGetLastError());
     Ctr c;
     if (sk_sync_counters(o, &c)) return 1;
     if (o->prof_on) {
         float ms = 0.f;
-        SHIP(o, hipEventElapsedTime(&ms, o->ev0, o->ev1));
+        HIP_CHECK(o, hipEventElapsedTime(&ms, o->ev0, o->ev1));
         o->last_probe_ms = ms;
     }
     return sk_report(o, c.err);
@@ -575,9 +525,9 @@ API int arroyo_amd_strkey_profile(void *h, int enable,
                                   double *last_lookup_ms) {
     GpuStrKey *o = (GpuStrKey *)h;
     if (enable > 0 && !o->ev0) {
-        SHIP(o, hipSetDevice(o->cfg.device));
-        SHIP(o, hipEventCreate(&o->ev0));
-        SHIP(o, hipEventCreate(&o->ev1));
+        HIP_CHECK(o, hipSetDevice(o->cfg.device));
+        HIP_CHECK(o, o->event_create(&o->ev0));
+        HIP_CHECK(o, o->event_create(&o->ev1));
     }
     if (enable >= 0) o->prof_on = enable > 0;
     if (last_lookup_ms) *last_lookup_ms = o->last_probe_ms;
@@ -603,11 +553,11 @@ static int sk_stage(GpuStrKey *o, const int32_t *offsets, const uint8_t *data,
     }
     if (sk_grow(o, &o->d_off, &o->off_cap, n_rows + 1, 4)) return 1;
     if (sk_grow(o, &o->d_data, &o->data_cap, hi - lo + 1, 1)) return 1;
-    SHIP(o, hipMemcpyAsync(o->d_off, offsets, (size_t)(n_rows + 1) * 4,
-                           hipMemcpyHostToDevice, o->stream));
-    if (hi > lo)
-        SHIP(o, hipMemcpyAsync(o->d_data, data + lo, (size_t)(hi - lo),
+    HIP_CHECK(o, hipMemcpyAsync(o->d_off, offsets, (size_t)(n_rows + 1) * 4,
                                hipMemcpyHostToDevice, o->stream));
+    if (hi > lo)
+        HIP_CHECK(o, hipMemcpyAsync(o->d_data, data + lo, (size_t)(hi - lo),
+                                   hipMemcpyHostToDevice, o->stream));
     *bias = lo;
     return 0;
 }
@@ -631,12 +581,32 @@ API int arroyo_amd_strkey_encode(void *h, const int32_t *offsets,
     if (sk_encode_device(o, o->d_off, o->d_data, bias, n_rows, o->d_ids,
                          hashes_out ? o->d_hashes : nullptr))
         return 1;
-    SHIP(o, hipMemcpyAsync(ids_out, o->d_ids, (size_t)n_rows * 8,
-                           hipMemcpyDeviceToHost, o->stream));
-    if (hashes_out)
-        SHIP(o, hipMemcpyAsync(hashes_out, o->d_hashes, (size_t)n_rows * 8,
+    HIP_CHECK(o, hipMemcpyAsync(ids_out, o->d_ids, (size_t)n_rows * 8,
                                hipMemcpyDeviceToHost, o->stream));
-    SHIP(o, hipStreamSynchronize(o->stream));
+    if (hashes_out)
+        HIP_CHECK(o, hipMemcpyAsync(hashes_out, o->d_hashes, (size_t)n_rows * 8,
+                                   hipMemcpyDeviceToHost, o->stream));
+    HIP_CHECK(o, hipStreamSynchronize(o->stream));
+    return 0;
+}
+
+API void arroyo_amd_strkey_free_out(AmdStrBatch *out);
+
+/* a host allocation of an output batch failed: free the batch, say so */
+static int sk_out_oom(GpuStrKey *o, AmdStrBatch *out) {
+    arroyo_amd_strkey_free_out(out);
+    snprintf(o->err_msg, sizeof o->err_msg,
+             "strkey output: host allocation failed");
+    return 1;
+}
+
+static int sk_empty_out(GpuStrKey *o, AmdStrBatch *out) {
+    out->n_rows = 0;
+    out->ids = (int64_t *)malloc(8);
+    out->offsets = (int32_t *)malloc(4);
+    out->data = (uint8_t *)malloc(1);
+    if (!out->ids || !out->offsets || !out->data) return sk_out_oom(o, out);
+    out->offsets[0] = 0;
     return 0;
 }
 
@@ -646,11 +616,11 @@ struct DecTmp {
     int32_t *off = nullptr;
     uint8_t *data = nullptr;
     ~DecTmp() {
-        hipFree(lens);
-        hipFree(pos);
-        hipFree(cub);
-        hipFree(off);
-        hipFree(data);
+        (void)hipFree(lens);
+        (void)hipFree(pos);
+        (void)hipFree(cub);
+        (void)hipFree(off);
+        (void)hipFree(data);
     }
 };
 
@@ -659,26 +629,26 @@ struct DecTmp {
 static int sk_decode_device_ids(GpuStrKey *o, const int64_t *d_ids, int64_t n,
                                 AmdStrBatch *out) {
     DecTmp t;
-    SHIP(o, hipSetDevice(o->cfg.device));
-    SHIP(o, hipMalloc((void **)&t.lens, (size_t)n * 8));
-    SHIP(o, hipMalloc((void **)&t.pos, (size_t)n * 8));
-    SHIP(o, hipMalloc((void **)&t.off, (size_t)(n + 1) * 4));
+    HIP_CHECK(o, hipSetDevice(o->cfg.device));
+    HIP_CHECK(o, hipMalloc((void **)&t.lens, (size_t)n * 8));
+    HIP_CHECK(o, hipMalloc((void **)&t.pos, (size_t)n * 8));
+    HIP_CHECK(o, hipMalloc((void **)&t.off, (size_t)(n + 1) * 4));
     size_t cub_bytes = 0;
-    SHIP(o, hipcub::DeviceScan::ExclusiveSum(nullptr, cub_bytes, t.lens,
-                                             t.pos, (int)n));
-    SHIP(o, hipMalloc(&t.cub, cub_bytes ? cub_bytes : 1));
-    SHIP(o, hipMemsetAsync(o->T.ctr, 0, 8, o->stream));
-    const int grid = sk_grid(n);
+    HIP_CHECK(o, hipcub::DeviceScan::ExclusiveSum(nullptr, cub_bytes, t.lens,
+                                                 t.pos, (int)n));
+    HIP_CHECK(o, hipMalloc(&t.cub, cub_bytes ? cub_bytes : 1));
+    HIP_CHECK(o, hipMemsetAsync(o->T.ctr, 0, 8, o->stream));
+    const int grid = grid_for(n, 2048);
     hipLaunchKernelGGL(k_strkey_dec_len, dim3(grid), dim3(256), 0, o->stream,
                        o->T, d_ids, n, t.lens);
-    SHIP(o, hipGetLastError());
-    SHIP(o, hipcub::DeviceScan::ExclusiveSum(t.cub, cub_bytes, t.lens, t.pos,
-                                             (int)n, o->stream));
+    HIP_CHECK(o, hipGetLastError());
+    HIP_CHECK(o, hipcub::DeviceScan::ExclusiveSum(t.cub, cub_bytes, t.lens,
+                                                  t.pos, (int)n, o->stream));
     int64_t tail[2] = {0, 0};
-    SHIP(o, hipMemcpyAsync(&tail[0], t.pos + (n - 1), 8,
-                           hipMemcpyDeviceToHost, o->stream));
-    SHIP(o, hipMemcpyAsync(&tail[1], t.lens + (n - 1), 8,
-                           hipMemcpyDeviceToHost, o->stream));
+    HIP_CHECK(o, hipMemcpyAsync(&tail[0], t.pos + (n - 1), 8,
+                               hipMemcpyDeviceToHost, o->stream));
+    HIP_CHECK(o, hipMemcpyAsync(&tail[1], t.lens + (n - 1), 8,
+                               hipMemcpyDeviceToHost, o->stream));
     Ctr c;
     if (sk_sync_counters(o, &c)) return 1;
     if (c.err) return sk_report(o, c.err);
@@ -690,27 +660,21 @@ static int sk_decode_device_ids(GpuStrKey *o, const int64_t *d_ids, int64_t n,
                  (long long)total);
         return 1;
     }
-    SHIP(o, hipMalloc((void **)&t.data, total ? (size_t)total : 1));
+    HIP_CHECK(o, hipMalloc((void **)&t.data, total ? (size_t)total : 1));
     hipLaunchKernelGGL(k_strkey_dec_gather, dim3(grid), dim3(256), 0,
                        o->stream, o->T, d_ids, (const int64_t *)t.pos,
                        (const int64_t *)t.lens, n, t.off, t.data);
-    SHIP(o, hipGetLastError());
+    HIP_CHECK(o, hipGetLastError());
     out->offsets = (int32_t *)malloc((size_t)(n + 1) * 4);
     out->data = (uint8_t *)malloc(total ? (size_t)total : 1);
-    SHIP(o, hipMemcpyAsync(out->offsets, t.off, (size_t)(n + 1) * 4,
-                           hipMemcpyDeviceToHost, o->stream));
-    if (total)
-        SHIP(o, hipMemcpyAsync(out->data, t.data, (size_t)total,
+    if (!out->offsets || !out->data) return sk_out_oom(o, out);
+    HIP_CHECK(o, hipMemcpyAsync(out->offsets, t.off, (size_t)(n + 1) * 4,
                                hipMemcpyDeviceToHost, o->stream));
-    SHIP(o, hipStreamSynchronize(o->stream));
+    if (total)
+        HIP_CHECK(o, hipMemcpyAsync(out->data, t.data, (size_t)total,
+                                   hipMemcpyDeviceToHost, o->stream));
+    HIP_CHECK(o, hipStreamSynchronize(o->stream));
     return 0;
-}
-
-static void sk_empty_out(AmdStrBatch *out) {
-    out->n_rows = 0;
-    out->ids = (int64_t *)malloc(8);
-    out->offsets = (int32_t *)calloc(1, 4);
-    out->data = (uint8_t *)malloc(1);
 }
 
 API void arroyo_amd_strkey_free_out(AmdStrBatch *out) {
@@ -730,13 +694,10 @@ API int arroyo_amd_strkey_decode(void *h, const int64_t *ids, int64_t n_rows,
                  (long long)n_rows);
         return 1;
     }
-    if (n_rows == 0) {
-        sk_empty_out(out);
-        return 0;
-    }
+    if (n_rows == 0) return sk_empty_out(o, out);
     if (sk_grow(o, &o->d_ids, &o->ids_cap, n_rows, 8)) return 1;
-    SHIP(o, hipMemcpyAsync(o->d_ids, ids, (size_t)n_rows * 8,
-                           hipMemcpyHostToDevice, o->stream));
+    HIP_CHECK(o, hipMemcpyAsync(o->d_ids, ids, (size_t)n_rows * 8,
+                               hipMemcpyHostToDevice, o->stream));
     int rc = sk_decode_device_ids(o, o->d_ids, n_rows, out);
     if (rc) {
         arroyo_amd_strkey_free_out(out);
@@ -744,6 +705,7 @@ API int arroyo_amd_strkey_decode(void *h, const int64_t *ids, int64_t n_rows,
     }
     out->n_rows = n_rows;
     out->ids = (int64_t *)malloc((size_t)n_rows * 8);
+    if (!out->ids) return sk_out_oom(o, out);
     memcpy(out->ids, ids, (size_t)n_rows * 8);
     return 0;
 }
@@ -760,10 +722,10 @@ struct DrainTmp {
     int64_t *flags = nullptr, *pos = nullptr, *ids = nullptr;
     void *cub = nullptr;
     ~DrainTmp() {
-        hipFree(flags);
-        hipFree(pos);
-        hipFree(ids);
-        hipFree(cub);
+        (void)hipFree(flags);
+        (void)hipFree(pos);
+        (void)hipFree(ids);
+        (void)hipFree(cub);
     }
 };
 
@@ -771,29 +733,27 @@ API int arroyo_amd_strkey_checkpoint_drain(void *h, AmdStrBatch *out) {
     GpuStrKey *o = (GpuStrKey *)h;
     memset(out, 0, sizeof *out);
     const int64_t n = (int64_t)o->n_live;
-    if (n == 0) {
-        sk_empty_out(out);
-        return 0;
-    }
+    if (n == 0) return sk_empty_out(o, out);
     DrainTmp t;
     const int64_t cap = (int64_t)o->cap;
-    SHIP(o, hipSetDevice(o->cfg.device));
-    SHIP(o, hipMalloc((void **)&t.flags, (size_t)cap * 8));
-    SHIP(o, hipMalloc((void **)&t.pos, (size_t)cap * 8));
-    SHIP(o, hipMalloc((void **)&t.ids, (size_t)n * 8));
+    HIP_CHECK(o, hipSetDevice(o->cfg.device));
+    HIP_CHECK(o, hipMalloc((void **)&t.flags, (size_t)cap * 8));
+    HIP_CHECK(o, hipMalloc((void **)&t.pos, (size_t)cap * 8));
+    HIP_CHECK(o, hipMalloc((void **)&t.ids, (size_t)n * 8));
     size_t cub_bytes = 0;
-    SHIP(o, hipcub::DeviceScan::ExclusiveSum(nullptr, cub_bytes, t.flags,
-                                             t.pos, (int)cap));
-    SHIP(o, hipMalloc(&t.cub, cub_bytes ? cub_bytes : 1));
-    const int grid = sk_grid(cap);
+    HIP_CHECK(o, hipcub::DeviceScan::ExclusiveSum(nullptr, cub_bytes, t.flags,
+                                                 t.pos, (int)cap));
+    HIP_CHECK(o, hipMalloc(&t.cub, cub_bytes ? cub_bytes : 1));
+    const int grid = grid_for(cap, 2048);
     hipLaunchKernelGGL(k_strkey_live_flags, dim3(grid), dim3(256), 0,
                        o->stream, o->T, t.flags);
-    SHIP(o, hipcub::DeviceScan::ExclusiveSum(t.cub, cub_bytes, t.flags, t.pos,
-                                             (int)cap, o->stream));
+    HIP_CHECK(o, hipcub::DeviceScan::ExclusiveSum(t.cub, cub_bytes, t.flags,
+                                                  t.pos, (int)cap,
+                                                  o->stream));
     hipLaunchKernelGGL(k_strkey_live_ids, dim3(grid), dim3(256), 0, o->stream,
                        o->T, (const int64_t *)t.flags, (const int64_t *)t.pos,
                        t.ids);
-    SHIP(o, hipGetLastError());
+    HIP_CHECK(o, hipGetLastError());
     int rc = sk_decode_device_ids(o, t.ids, n, out);
     if (rc) {
         arroyo_amd_strkey_free_out(out);
@@ -801,11 +761,12 @@ API int arroyo_amd_strkey_checkpoint_drain(void *h, AmdStrBatch *out) {
     }
     out->n_rows = n;
     out->ids = (int64_t *)malloc((size_t)n * 8);
+    if (!out->ids) return sk_out_oom(o, out);
     hipError_t e =
         hipMemcpy(out->ids, t.ids, (size_t)n * 8, hipMemcpyDeviceToHost);
     if (e != hipSuccess) {
         arroyo_amd_strkey_free_out(out);
-        SHIP(o, e);
+        HIP_CHECK(o, e);
     }
     return 0;
 }
@@ -832,10 +793,10 @@ API int arroyo_amd_strkey_restore(void *h, const int64_t *ids,
     int64_t bias = 0;
     if (sk_stage(o, offsets, data, n_rows, &bias)) return 1;
     if (sk_grow(o, &o->d_ids, &o->ids_cap, n_rows, 8)) return 1;
-    SHIP(o, hipMemcpyAsync(o->d_ids, ids, (size_t)n_rows * 8,
-                           hipMemcpyHostToDevice, o->stream));
-    SHIP(o, hipMemsetAsync(o->T.ctr, 0, 8, o->stream));
-    const int grid = sk_grid(n_rows);
+    HIP_CHECK(o, hipMemcpyAsync(o->d_ids, ids, (size_t)n_rows * 8,
+                               hipMemcpyHostToDevice, o->stream));
+    HIP_CHECK(o, hipMemsetAsync(o->T.ctr, 0, 8, o->stream));
+    const int grid = grid_for(n_rows, 2048);
     hipLaunchKernelGGL(k_strkey_check_offsets, dim3(grid), dim3(256), 0,
                        o->stream, (const int32_t *)o->d_off, n_rows, o->T.ctr);
     hipLaunchKernelGGL(k_strkey_restore_place, dim3(grid), dim3(256), 0,
@@ -846,15 +807,15 @@ API int arroyo_amd_strkey_restore(void *h, const int64_t *ids,
                        o->stream, o->T, (const int64_t *)o->d_ids,
                        (const int32_t *)o->d_off, (const uint8_t *)o->d_data,
                        bias, n_rows);
-    SHIP(o, hipGetLastError());
+    HIP_CHECK(o, hipGetLastError());
     Ctr c;
     if (sk_sync_counters(o, &c)) return 1;
     if (c.err) {
         /* a failed restore leaves the handle empty, not half loaded */
         int rc = sk_report(o, c.err);
-        SHIP(o, hipMemsetAsync(o->T.slots, 0, o->cap * 8, o->stream));
-        SHIP(o, hipMemsetAsync(o->T.ctr, 0, sizeof(Ctr), o->stream));
-        SHIP(o, hipStreamSynchronize(o->stream));
+        HIP_CHECK(o, hipMemsetAsync(o->T.slots, 0, o->cap * 8, o->stream));
+        HIP_CHECK(o, hipMemsetAsync(o->T.ctr, 0, sizeof(Ctr), o->stream));
+        HIP_CHECK(o, hipStreamSynchronize(o->stream));
         o->n_live = o->occupied = o->arena_used = 0;
         return rc;
     }
@@ -862,8 +823,5 @@ API int arroyo_amd_strkey_restore(void *h, const int64_t *ids,
 }
 
 API void arroyo_amd_strkey_destroy(void *h) {
-    GpuStrKey *o = (GpuStrKey *)h;
-    if (!o) return;
-    hipStreamSynchronize(o->stream);
-    sk_release(o);
+    delete (GpuStrKey *)h;   /* ~OpBase drains the stream first */
 }

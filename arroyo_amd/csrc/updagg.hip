@@ -55,20 +55,10 @@
  * the reference's debezium_agg / filter_updating_aggregates golden
  * vectors) by tests/test_updagg.py.
  */
-#include <hip/hip_runtime.h>
-
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-#include "../../include/arroyo_amd_types.h"
-
-#define API extern "C" __attribute__((visibility("default")))
+#include "op_common.h"
 
 namespace updagg {
 
-#define EMPTY_KEY (-1LL)
 #define UERR_TABLE_FULL 1
 #define UERR_POOL_FULL  2
 #define UERR_OUT_CAP    3
@@ -87,13 +77,6 @@ __host__ __device__ inline uint64_t enc_max(int64_t v) {
 }
 __host__ __device__ inline int64_t dec_max(uint64_t e) {
     return (int64_t)(e ^ 0x8000000000000000ULL);
-}
-
-__device__ inline uint64_t hash64(uint64_t x) {
-    x += 0x9e3779b97f4a7c15ULL;
-    x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ULL;
-    x = (x ^ (x >> 27)) * 0x94d049bb133111ebULL;
-    return x ^ (x >> 31);
 }
 
 #define UAGG_MAX_SW 128  /* total state words cap per key */
@@ -1168,18 +1151,14 @@ k_updagg_restore(URestoreArgs R) {
 
 using namespace updagg;
 
-static char g_ua_err[256];
-
-struct GpuUpdAgg {
+struct GpuUpdAgg : OpBase {
     AmdUpdatingConfig cfg;
     AggSpec agg;
     UStore store;
     uint32_t cur_epoch;
     int64_t *d_out[UAGG_MAX_SW + AMD_MAX_AGGS + 4];
     unsigned long long *d_n_out;
-    int *d_err;
-    int64_t *stg_h[12], *stg_d[12];
-    int64_t stg_cap;
+    Staging stg;
     int n_in_cols, out_cols, drain0_cols, drain1_cols;
     int64_t out_cap;
     int has_ord;                /* config has MEDIAN / MIN_RETRACT / MAX_RETRACT */
@@ -1192,10 +1171,8 @@ struct GpuUpdAgg {
     uint64_t *d_bm;             /* [n_aggs * bm_words] packed output bitmaps */
     int64_t bm_words;
     unsigned int *d_nullcols;
-    uint64_t *stg_vh[8], *stg_vd[8];   /* input bitmap staging, per value
-                                          column, stg_cap / 64 words */
-    hipStream_t stream;
-    char err_msg[512];
+    Staging stg_v;              /* input bitmap staging, per value column,
+                                   stg.cap / 64 words */
 };
 
 static bool ua_is_ord(int op) {
@@ -1203,34 +1180,24 @@ static bool ua_is_ord(int op) {
            op == AMD_AGG_MAX_RETRACT;
 }
 
-#define UHIP(o, call)                                                        \
-    do {                                                                      \
-        hipError_t _e = (call);                                               \
-        if (_e != hipSuccess) {                                               \
-            snprintf((o)->err_msg, sizeof (o)->err_msg, "%s:%d hip: %s",      \
-                     __FILE__, __LINE__, hipGetErrorString(_e));              \
-            return 1;                                                         \
-        }                                                                     \
-    } while (0)
-
 API void *arroyo_amd_updagg_create(const AmdUpdatingConfig *cfg) {
     if (!cfg || cfg->n_keys < 0 || cfg->n_keys > 1 || cfg->n_value_cols < 0 ||
         cfg->n_value_cols > 8 || cfg->n_aggs < 1 ||
         cfg->n_aggs > AMD_MAX_AGGS) {
-        snprintf(g_ua_err, sizeof g_ua_err, "invalid updagg config");
+        snprintf(g_create_err, sizeof g_create_err, "invalid updagg config");
         return nullptr;
     }
     int has_ord = 0;
     for (int i = 0; i < cfg->n_aggs; i++) {
         int op = cfg->agg_ops[i];
         if (op < AMD_AGG_COUNT || op > AMD_AGG_MAX_RETRACT) {
-            snprintf(g_ua_err, sizeof g_ua_err,
+            snprintf(g_create_err, sizeof g_create_err,
                      "invalid updagg config: unknown aggregate op %d", op);
             return nullptr;
         }
         if (ua_is_ord(op)) {
             if (cfg->agg_col[i] < 0 || cfg->agg_col[i] >= cfg->n_value_cols) {
-                snprintf(g_ua_err, sizeof g_ua_err,
+                snprintf(g_create_err, sizeof g_create_err,
                          "invalid updagg config: aggregate op %d needs a "
                          "value column", op);
                 return nullptr;
@@ -1239,7 +1206,7 @@ API void *arroyo_amd_updagg_create(const AmdUpdatingConfig *cfg) {
         }
     }
     if (cfg->null_semantics != 0 && cfg->null_semantics != 1) {
-        snprintf(g_ua_err, sizeof g_ua_err,
+        snprintf(g_create_err, sizeof g_create_err,
                  "invalid updagg config: null_semantics %d (0 or 1)",
                  cfg->null_semantics);
         return nullptr;
@@ -1258,7 +1225,7 @@ API void *arroyo_amd_updagg_create(const AmdUpdatingConfig *cfg) {
         o->agg.SW += ua_width(cfg->agg_ops[i], o->ns);
     }
     if (o->agg.SW > UAGG_MAX_SW) {
-        snprintf(g_ua_err, sizeof g_ua_err,
+        snprintf(g_create_err, sizeof g_create_err,
                  "aggregate state too wide (%d words > %d)", o->agg.SW,
                  UAGG_MAX_SW);
         delete o;
@@ -1274,121 +1241,79 @@ API void *arroyo_amd_updagg_create(const AmdUpdatingConfig *cfg) {
     o->drain1_cols = cfg->n_keys + 3;
     o->cur_epoch = 1;
     if (hipSetDevice(cfg->device) != hipSuccess) {
-        snprintf(g_ua_err, sizeof g_ua_err,
+        snprintf(g_create_err, sizeof g_create_err,
                  "hipSetDevice(%d) failed: no HIP device (no CPU fallback)",
                  cfg->device);
         delete o;
         return nullptr;
     }
-    hipError_t e;
-    auto fail = [&](const char *what, hipError_t e2) {
-        snprintf(g_ua_err, sizeof g_ua_err, "%s: %s", what,
-                 hipGetErrorString(e2));
-        delete o;
-        return nullptr;
-    };
-#define UALLOC(p, bytes)                                                      \
-    if ((e = hipMalloc((void **)&(p), (bytes))) != hipSuccess)                \
-        return fail(#p, e);
     size_t C1 = (size_t)o->store.C + 1;
     size_t na = cfg->n_aggs;
-    UALLOC(o->store.keys, C1 * 8);
-    UALLOC(o->store.epoch, C1 * 4);
-    UALLOC(o->store.rows, C1 * 8);
-    UALLOC(o->store.st, C1 * (size_t)o->agg.SW * 8);
-    UALLOC(o->store.last, C1 * na * 8);
-    UALLOC(o->store.emitted, C1 * 4);
-    UALLOC(o->store.head, C1 * 8 * 4);
-    UALLOC(o->store.pool, (size_t)o->store.pool_cap * sizeof(Node));
-    UALLOC(o->store.pool_cur, 8);
+    OP_ALLOC(o, o->store.keys, C1 * 8, 0xFF);
+    OP_ALLOC(o, o->store.epoch, C1 * 4, 0);
+    OP_ALLOC(o, o->store.rows, C1 * 8, 0);
+    /* every state's identity is the zero pattern (enc_min/enc_max map the
+     * MIN/MAX identities to 0; f64 sums start at +0.0 = zero bits; bit
+     * counters at 0), so a plain memset initializes the plane */
+    OP_ALLOC(o, o->store.st, C1 * (size_t)o->agg.SW * 8, 0);
+    OP_ALLOC(o, o->store.last, C1 * na * 8);
+    OP_ALLOC(o, o->store.emitted, C1 * 4, 0);
+    OP_ALLOC(o, o->store.head, C1 * 8 * 4, 0xFF);
+    OP_ALLOC(o, o->store.pool, (size_t)o->store.pool_cap * sizeof(Node));
+    OP_ALLOC(o, o->store.pool_cur, 8, 0);
     if (o->has_ord) {
         /* no reset needed between flushes: k_updagg_ordstat writes ord for
          * exactly the (slot, agg) pairs k_updagg_flush then reads */
-        UALLOC(o->store.ord, C1 * na * 8);
-        UALLOC(o->d_arena, (size_t)o->store.pool_cap * sizeof(OrdEnt));
-        UALLOC(o->d_arena_cur, 8);
+        OP_ALLOC(o, o->store.ord, C1 * na * 8);
+        OP_ALLOC(o, o->d_arena, (size_t)o->store.pool_cap * sizeof(OrdEnt));
+        OP_ALLOC(o, o->d_arena_cur, 8);
     }
     int max_out = o->drain0_cols;
     if (o->drain1_cols > max_out) max_out = o->drain1_cols;
     if (o->out_cols > max_out) max_out = o->out_cols;
     for (int i = 0; i < max_out; i++)
-        UALLOC(o->d_out[i], (size_t)o->out_cap * 8);
-    UALLOC(o->d_n_out, 8);
-    UALLOC(o->d_err, 4);
+        OP_ALLOC(o, o->d_out[i], (size_t)o->out_cap * 8);
+    OP_ALLOC(o, o->d_n_out, 8);
+    OP_ALLOC(o, o->d_err, 4, 0);
     if (o->ns) {
         o->bm_words = o->out_cap / 64 + 1;
-        UALLOC(o->d_lastv, C1 * 4);
-        UALLOC(o->d_vmask, (size_t)o->out_cap * 4);
-        UALLOC(o->d_bm, na * (size_t)o->bm_words * 8);
-        UALLOC(o->d_nullcols, 4);
-        hipMemset(o->d_lastv, 0, C1 * 4);
+        OP_ALLOC(o, o->d_lastv, C1 * 4, 0);
+        OP_ALLOC(o, o->d_vmask, (size_t)o->out_cap * 4);
+        OP_ALLOC(o, o->d_bm, na * (size_t)o->bm_words * 8);
+        OP_ALLOC(o, o->d_nullcols, 4);
     }
-#undef UALLOC
-    hipMemset(o->store.keys, 0xFF, C1 * 8);
-    hipMemset(o->store.epoch, 0, C1 * 4);
-    hipMemset(o->store.rows, 0, C1 * 8);
-    hipMemset(o->store.emitted, 0, C1 * 4);
-    hipMemset(o->store.head, 0xFF, C1 * 8 * 4);
-    hipMemset(o->store.pool_cur, 0, 8);
-    hipMemset(o->d_err, 0, 4);
-    /* every state's identity is the zero pattern (enc_min/enc_max map the
-     * MIN/MAX identities to 0; f64 sums start at +0.0 = zero bits; bit
-     * counters at 0), so a plain memset initializes the plane */
-    hipMemset(o->store.st, 0, C1 * (size_t)o->agg.SW * 8);
-    hipStreamCreate(&o->stream);
-    o->stg_cap = 1 << 20;
-    for (int c = 0; c < o->n_in_cols; c++) {
-        if (hipHostMalloc((void **)&o->stg_h[c], (size_t)o->stg_cap * 8) !=
-                hipSuccess ||
-            hipMalloc((void **)&o->stg_d[c], (size_t)o->stg_cap * 8) !=
-                hipSuccess) {
-            snprintf(g_ua_err, sizeof g_ua_err, "updagg staging alloc failed");
-            delete o;
-            return nullptr;
-        }
-    }
-    for (int v = 0; o->ns && v < cfg->n_value_cols; v++) {
-        size_t bytes = (size_t)(o->stg_cap / 64) * 8;
-        if (hipHostMalloc((void **)&o->stg_vh[v], bytes) != hipSuccess ||
-            hipMalloc((void **)&o->stg_vd[v], bytes) != hipSuccess) {
-            snprintf(g_ua_err, sizeof g_ua_err,
-                     "updagg validity staging alloc failed");
-            delete o;
-            return nullptr;
-        }
-    }
+    OP_TRY(o, "hipStreamCreate", o->stream_create(&o->stream));
+    OP_TRY_MSG(o, "updagg staging alloc failed",
+               o->stg.alloc(o, o->n_in_cols, 1 << 20));
+    if (o->ns)
+        OP_TRY_MSG(o, "updagg validity staging alloc failed",
+                   o->stg_v.alloc(o, cfg->n_value_cols, o->stg.cap / 64));
     return o;
 }
 
 API const char *arroyo_amd_updagg_last_error(void *h) {
-    return h ? ((GpuUpdAgg *)h)->err_msg : g_ua_err;
+    return h ? ((GpuUpdAgg *)h)->err_msg : g_create_err;
 }
 
-static int ua_check_err(GpuUpdAgg *o) {
-    int e = 0;
-    UHIP(o, hipMemcpyAsync(&e, o->d_err, 4, hipMemcpyDeviceToHost,
-                           o->stream));
-    UHIP(o, hipStreamSynchronize(o->stream));
-    if (!e) return 0;
-    const char *msg =
-        e == UERR_TABLE_FULL ? "key table full; raise log2_capacity"
-        : e == UERR_POOL_FULL
-            ? "distinct-value node pool full; raise log2_nodes"
-        : e == UERR_OUT_CAP ? "output buffer full; raise log2_out_cap"
-        : e == UERR_RETRACT
-            ? "MIN/MAX do not support retraction (append-only here)"
-        : e == UERR_ORD_ROWS
-            ? "ordered aggregate: retraction without a matching append"
-        : e == UERR_ORD_CHAIN
-            ? "ordered aggregate: value chain exceeds the node pool"
-            : "device error";
-    snprintf(o->err_msg, sizeof o->err_msg, "%s", msg);
+static const char *ua_err_msg(int e) {
+    return e == UERR_TABLE_FULL ? "key table full; raise log2_capacity"
+           : e == UERR_POOL_FULL
+               ? "distinct-value node pool full; raise log2_nodes"
+           : e == UERR_OUT_CAP ? "output buffer full; raise log2_out_cap"
+           : e == UERR_RETRACT
+               ? "MIN/MAX do not support retraction (append-only here)"
+           : e == UERR_ORD_ROWS
+               ? "ordered aggregate: retraction without a matching append"
+           : e == UERR_ORD_CHAIN
+               ? "ordered aggregate: value chain exceeds the node pool"
+               : "device error";
+}
+
+static int ua_check_cols(GpuUpdAgg *o, int32_t n_cols) {
+    if (n_cols == o->n_in_cols) return 0;
+    snprintf(o->err_msg, sizeof o->err_msg, "expected %d cols, got %d",
+             o->n_in_cols, n_cols);
     return 1;
-}
-
-static int ua_grid(int64_t want_threads) {
-    int64_t want = (want_threads + 255) / 256;
-    return (int)(want > 2048 ? 2048 : (want < 1 ? 1 : want));
 }
 
 static void ua_fill_update_args(GpuUpdAgg *o, UpdateArgs *A, int64_t n_rows) {
@@ -1410,11 +1335,7 @@ static int ua_check_nullable(GpuUpdAgg *o, const uint8_t *const *validity,
                  "null_semantics = 1");
         return 1;
     }
-    if (n_cols != o->n_in_cols) {
-        snprintf(o->err_msg, sizeof o->err_msg, "expected %d cols, got %d",
-                 o->n_in_cols, n_cols);
-        return 1;
-    }
+    if (ua_check_cols(o, n_cols)) return 1;
     if (validity) {
         if (o->cfg.n_keys && validity[0]) {
             snprintf(o->err_msg, sizeof o->err_msg,
@@ -1433,43 +1354,39 @@ static int ua_check_nullable(GpuUpdAgg *o, const uint8_t *const *validity,
 }
 
 /* host ingest; validity == nullptr (or an entry of it) = all valid.  Chunks
- * are stg_cap = 2^20 rows, so a chunk starts on a bitmap byte boundary. */
+ * are stg.cap = 2^20 rows, so a chunk starts on a bitmap byte boundary. */
 static int ua_process_host(GpuUpdAgg *o, const int64_t *const *cols,
                            const uint8_t *const *validity, int32_t n_cols,
                            int64_t n_rows) {
     int64_t done = 0;
     while (done < n_rows) {
         int64_t take = n_rows - done;
-        if (take > o->stg_cap) take = o->stg_cap;
+        if (take > o->stg.cap) take = o->stg.cap;
         UpdateArgsN N = {};
         UpdateArgs &A = N.A;
-        for (int c = 0; c < n_cols; c++) {
-            memcpy(o->stg_h[c], cols[c] + done, (size_t)take * 8);
-            UHIP(o, hipMemcpyAsync(o->stg_d[c], o->stg_h[c],
-                                   (size_t)take * 8, hipMemcpyHostToDevice,
-                                   o->stream));
-            A.cols[c] = o->stg_d[c];
-        }
+        if (o->stg.stage_chunk(o, cols, n_cols, done, take, A.cols)) return 1;
         for (int v = 0; validity && v < o->cfg.n_value_cols; v++) {
             const uint8_t *bm = validity[o->cfg.n_keys + v];
             if (!bm) continue;
             size_t nbytes = (size_t)((take + 7) / 8);
             size_t nwords = (size_t)((take + 63) / 64);
-            o->stg_vh[v][nwords - 1] = 0;   /* pad the last word */
-            memcpy(o->stg_vh[v], bm + done / 8, nbytes);
-            UHIP(o, hipMemcpyAsync(o->stg_vd[v], o->stg_vh[v], nwords * 8,
-                                   hipMemcpyHostToDevice, o->stream));
-            N.valid[v] = o->stg_vd[v];
+            o->stg_v.h[v][nwords - 1] = 0;   /* pad the last word */
+            memcpy(o->stg_v.h[v], bm + done / 8, nbytes);
+            HIP_CHECK(o, hipMemcpyAsync(o->stg_v.d[v], o->stg_v.h[v],
+                                        nwords * 8, hipMemcpyHostToDevice,
+                                        o->stream));
+            N.valid[v] = (const uint64_t *)o->stg_v.d[v];
         }
         ua_fill_update_args(o, &A, take);
         if (o->ns)
-            hipLaunchKernelGGL(k_updagg_update_nullable, dim3(ua_grid(take)),
+            hipLaunchKernelGGL(k_updagg_update_nullable,
+                               dim3(grid_for(take, 2048)),
                                dim3(256), 0, o->stream, N);
         else
-            hipLaunchKernelGGL(k_updagg_update, dim3(ua_grid(take)),
+            hipLaunchKernelGGL(k_updagg_update, dim3(grid_for(take, 2048)),
                                dim3(256), 0, o->stream, A);
-        UHIP(o, hipGetLastError());
-        UHIP(o, hipStreamSynchronize(o->stream));
+        HIP_CHECK(o, hipGetLastError());
+        HIP_CHECK(o, hipStreamSynchronize(o->stream));
         done += take;
     }
     return 0;
@@ -1493,23 +1410,21 @@ static int ua_process_device(GpuUpdAgg *o, const int64_t *const *dcols,
     }
     ua_fill_update_args(o, &A, n_rows);
     if (o->ns)
-        hipLaunchKernelGGL(k_updagg_update_nullable, dim3(ua_grid(n_rows)),
+        hipLaunchKernelGGL(k_updagg_update_nullable,
+                           dim3(grid_for(n_rows, 2048)),
                            dim3(256), 0, o->stream, N);
     else
-        hipLaunchKernelGGL(k_updagg_update, dim3(ua_grid(n_rows)), dim3(256),
+        hipLaunchKernelGGL(k_updagg_update, dim3(grid_for(n_rows, 2048)),
+                           dim3(256),
                            0, o->stream, A);
-    UHIP(o, hipGetLastError());
+    HIP_CHECK(o, hipGetLastError());
     return 0;
 }
 
 API int arroyo_amd_updagg_process_batch(void *h, const int64_t *const *cols,
                                         int32_t n_cols, int64_t n_rows) {
     GpuUpdAgg *o = (GpuUpdAgg *)h;
-    if (n_cols != o->n_in_cols) {
-        snprintf(o->err_msg, sizeof o->err_msg, "expected %d cols, got %d",
-                 o->n_in_cols, n_cols);
-        return 1;
-    }
+    if (ua_check_cols(o, n_cols)) return 1;
     return ua_process_host(o, cols, nullptr, n_cols, n_rows);
 }
 
@@ -1518,11 +1433,7 @@ API int arroyo_amd_updagg_process_batch_device(void *h,
                                                int32_t n_cols,
                                                int64_t n_rows) {
     GpuUpdAgg *o = (GpuUpdAgg *)h;
-    if (n_cols != o->n_in_cols) {
-        snprintf(o->err_msg, sizeof o->err_msg, "expected %d cols, got %d",
-                 o->n_in_cols, n_cols);
-        return 1;
-    }
+    if (ua_check_cols(o, n_cols)) return 1;
     return ua_process_device(o, dcols, nullptr, n_cols, n_rows);
 }
 
@@ -1550,52 +1461,60 @@ API int arroyo_amd_updagg_process_batch_nullable_device(
 static int ua_fill_validity(GpuUpdAgg *o, AmdOutBatch *out) {
     if (!o->ns) return 0;
     int64_t n = out->n_rows;
-    out->validity = (uint8_t **)calloc(o->out_cols, sizeof(uint8_t *));
-    if (!out->validity) {
+    if (out_alloc_validity(out)) {
         snprintf(o->err_msg, sizeof o->err_msg,
                  "validity bitmap table allocation failed");
         return 1;
     }
     if (n == 0) return 0;
     int na = o->cfg.n_aggs;
-    UHIP(o, hipMemsetAsync(o->d_nullcols, 0, 4, o->stream));
+    HIP_CHECK(o, hipMemsetAsync(o->d_nullcols, 0, 4, o->stream));
     PackArgs P = {};
     P.vmask = o->d_vmask;
     P.n_rows = n;
     P.n_aggs = na;
     for (int a = 0; a < na; a++) P.bm[a] = o->d_bm + (size_t)a * o->bm_words;
     P.nullcols = o->d_nullcols;
-    hipLaunchKernelGGL(k_updagg_pack_validity, dim3(ua_grid(n)), dim3(256),
+    hipLaunchKernelGGL(k_updagg_pack_validity, dim3(grid_for(n, 2048)),
+                       dim3(256),
                        0, o->stream, P);
-    UHIP(o, hipGetLastError());
+    HIP_CHECK(o, hipGetLastError());
     unsigned int nullcols = 0;
-    UHIP(o, hipMemcpyAsync(&nullcols, o->d_nullcols, 4,
-                           hipMemcpyDeviceToHost, o->stream));
-    UHIP(o, hipStreamSynchronize(o->stream));
+    HIP_CHECK(o, hipMemcpyAsync(&nullcols, o->d_nullcols, 4,
+                                hipMemcpyDeviceToHost, o->stream));
+    HIP_CHECK(o, hipStreamSynchronize(o->stream));
     size_t nbytes = (size_t)((n + 7) / 8);
     for (int a = 0; a < na; a++) {
         if (!((nullcols >> a) & 1)) continue;
-        uint8_t *bm = (uint8_t *)malloc(nbytes);
+        uint8_t *bm = out_validity_col(out, o->cfg.n_keys + a);
         if (!bm) {
             snprintf(o->err_msg, sizeof o->err_msg,
                      "validity bitmap allocation failed (%zu bytes)", nbytes);
             return 1;
         }
-        out->validity[o->cfg.n_keys + a] = bm;
-        UHIP(o, hipMemcpyAsync(bm, P.bm[a], nbytes, hipMemcpyDeviceToHost,
-                               o->stream));
+        HIP_CHECK(o, hipMemcpyAsync(bm, P.bm[a], nbytes, hipMemcpyDeviceToHost,
+                                    o->stream));
     }
-    UHIP(o, hipStreamSynchronize(o->stream));
+    HIP_CHECK(o, hipStreamSynchronize(o->stream));
     return 0;
+}
+
+/* the emitted rows and their bitmaps into the allocated batch; an error
+ * leaves `out` freed and zeroed */
+static int ua_out_rows(GpuUpdAgg *o, AmdOutBatch *out, int64_t n) {
+    if (out_copy_cols(o, out, o->d_out, n)) return 1;
+    if (!ua_fill_validity(o, out)) return 0;
+    out_free_host(out);
+    return 1;
 }
 
 API int arroyo_amd_updagg_flush(void *h, AmdOutBatch *out) {
     GpuUpdAgg *o = (GpuUpdAgg *)h;
-    if (ua_check_err(o)) return 1;
-    UHIP(o, hipMemsetAsync(o->d_n_out, 0, 8, o->stream));
+    if (op_check_err(o, ua_err_msg)) return 1;
+    HIP_CHECK(o, hipMemsetAsync(o->d_n_out, 0, 8, o->stream));
     if (o->has_ord) {
         /* order-statistic pre-pass: one wave per 8 slots, grid-strided */
-        UHIP(o, hipMemsetAsync(o->d_arena_cur, 0, 8, o->stream));
+        HIP_CHECK(o, hipMemsetAsync(o->d_arena_cur, 0, 8, o->stream));
         OrdArgs R = {};
         R.store = o->store;
         R.agg = o->agg;
@@ -1607,12 +1526,13 @@ API int arroyo_amd_updagg_flush(void *h, AmdOutBatch *out) {
         int64_t waves = ((int64_t)o->store.C + 1 + 7) / 8;
         if (o->ns)
             hipLaunchKernelGGL(k_updagg_ordstat_nullable,
-                               dim3(ua_grid(waves * 64)),
+                               dim3(grid_for(waves * 64, 2048)),
                                dim3(64 * UORD_WAVES), 0, o->stream, R);
         else
-            hipLaunchKernelGGL(k_updagg_ordstat, dim3(ua_grid(waves * 64)),
+            hipLaunchKernelGGL(k_updagg_ordstat,
+                               dim3(grid_for(waves * 64, 2048)),
                                dim3(64 * UORD_WAVES), 0, o->stream, R);
-        UHIP(o, hipGetLastError());
+        HIP_CHECK(o, hipGetLastError());
     }
     FlushArgs F = {};
     F.store = o->store;
@@ -1627,25 +1547,24 @@ API int arroyo_amd_updagg_flush(void *h, AmdOutBatch *out) {
     F.vmask = o->d_vmask;
     if (o->ns)
         hipLaunchKernelGGL(k_updagg_flush_nullable,
-                           dim3(ua_grid((int64_t)o->store.C + 1)), dim3(256),
+                           dim3(grid_for((int64_t)o->store.C + 1, 2048)),
+                           dim3(256),
                            0, o->stream, F);
     else
         hipLaunchKernelGGL(k_updagg_flush,
-                           dim3(ua_grid((int64_t)o->store.C + 1)), dim3(256),
+                           dim3(grid_for((int64_t)o->store.C + 1, 2048)),
+                           dim3(256),
                            0, o->stream, F);
-    UHIP(o, hipGetLastError());
+    HIP_CHECK(o, hipGetLastError());
     unsigned long long n = 0;
-    UHIP(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
-                           o->stream));
-    UHIP(o, hipStreamSynchronize(o->stream));
-    if (ua_check_err(o)) return 1;
+    HIP_CHECK(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
+                                o->stream));
+    HIP_CHECK(o, hipStreamSynchronize(o->stream));
+    if (op_check_err(o, ua_err_msg)) return 1;
     o->cur_epoch++;
     if (out) {
-        memset(out, 0, sizeof *out);
-        out->n_rows = (int64_t)n;
-        out->n_cols = o->out_cols;
-        out->cols = (void **)calloc(o->out_cols, sizeof(void *));
-        out->is_f64 = (int32_t *)calloc(o->out_cols, sizeof(int32_t));
+        if (op_out_alloc(o, out, (int64_t)n, o->out_cols, __func__))
+            return 1;
         for (int a = 0; a < o->cfg.n_aggs; a++)
             if (o->cfg.agg_ops[a] == AMD_AGG_AVG ||
                 (o->cfg.agg_ops[a] >= AMD_AGG_STDDEV &&
@@ -1654,15 +1573,7 @@ API int arroyo_amd_updagg_flush(void *h, AmdOutBatch *out) {
                  o->cfg.agg_ops[a] <= AMD_AGG_REGR_SXY &&
                  o->cfg.agg_ops[a] != AMD_AGG_REGR_COUNT))
                 out->is_f64[o->cfg.n_keys + a] = 1;
-        for (int i = 0; i < o->out_cols; i++) {
-            out->cols[i] = malloc((size_t)(n ? n : 1) * 8);
-            if (n)
-                UHIP(o, hipMemcpyAsync(out->cols[i], o->d_out[i],
-                                       (size_t)n * 8, hipMemcpyDeviceToHost,
-                                       o->stream));
-        }
-        UHIP(o, hipStreamSynchronize(o->stream));
-        if (ua_fill_validity(o, out)) return 1;
+        if (ua_out_rows(o, out, (int64_t)n)) return 1;
     }
     return 0;
 }
@@ -1670,8 +1581,8 @@ API int arroyo_amd_updagg_flush(void *h, AmdOutBatch *out) {
 API int arroyo_amd_updagg_expire(void *h, int64_t idle_flushes,
                                  AmdOutBatch *out) {
     GpuUpdAgg *o = (GpuUpdAgg *)h;
-    if (ua_check_err(o)) return 1;
-    UHIP(o, hipMemsetAsync(o->d_n_out, 0, 8, o->stream));
+    if (op_check_err(o, ua_err_msg)) return 1;
+    HIP_CHECK(o, hipMemsetAsync(o->d_n_out, 0, 8, o->stream));
     ExpireArgs E = {};
     E.store = o->store;
     E.agg = o->agg;
@@ -1685,39 +1596,27 @@ API int arroyo_amd_updagg_expire(void *h, int64_t idle_flushes,
     E.lastv = o->d_lastv;
     E.vmask = o->d_vmask;
     hipLaunchKernelGGL(k_updagg_expire,
-                       dim3(ua_grid((int64_t)o->store.C + 1)), dim3(256), 0,
+                       dim3(grid_for((int64_t)o->store.C + 1, 2048)),
+                       dim3(256), 0,
                        o->stream, E);
-    UHIP(o, hipGetLastError());
+    HIP_CHECK(o, hipGetLastError());
     unsigned long long n = 0;
-    UHIP(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
-                           o->stream));
-    UHIP(o, hipStreamSynchronize(o->stream));
-    if (ua_check_err(o)) return 1;
-    if (out) {
-        memset(out, 0, sizeof *out);
-        out->n_rows = (int64_t)n;
-        out->n_cols = o->out_cols;
-        out->cols = (void **)calloc(o->out_cols, sizeof(void *));
-        out->is_f64 = (int32_t *)calloc(o->out_cols, sizeof(int32_t));
-        for (int i = 0; i < o->out_cols; i++) {
-            out->cols[i] = malloc((size_t)(n ? n : 1) * 8);
-            if (n)
-                UHIP(o, hipMemcpyAsync(out->cols[i], o->d_out[i],
-                                       (size_t)n * 8, hipMemcpyDeviceToHost,
-                                       o->stream));
-        }
-        UHIP(o, hipStreamSynchronize(o->stream));
-        if (ua_fill_validity(o, out)) return 1;
-    }
+    HIP_CHECK(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
+                                o->stream));
+    HIP_CHECK(o, hipStreamSynchronize(o->stream));
+    if (op_check_err(o, ua_err_msg)) return 1;
+    if (out && (op_out_alloc(o, out, (int64_t)n, o->out_cols, __func__) ||
+                ua_out_rows(o, out, (int64_t)n)))
+        return 1;
     return 0;
 }
 
 API int arroyo_amd_updagg_checkpoint_drain(void *h, int32_t which,
                                            AmdOutBatch *out) {
     GpuUpdAgg *o = (GpuUpdAgg *)h;
-    if (ua_check_err(o)) return 1;
+    if (op_check_err(o, ua_err_msg)) return 1;
     int ncols = which == 0 ? o->drain0_cols : o->drain1_cols;
-    UHIP(o, hipMemsetAsync(o->d_n_out, 0, 8, o->stream));
+    HIP_CHECK(o, hipMemsetAsync(o->d_n_out, 0, 8, o->stream));
     UDrainArgs D = {};
     D.store = o->store;
     D.agg = o->agg;
@@ -1729,27 +1628,17 @@ API int arroyo_amd_updagg_checkpoint_drain(void *h, int32_t which,
     D.err = o->d_err;
     D.lastv = o->d_lastv;
     hipLaunchKernelGGL(k_updagg_drain,
-                       dim3(ua_grid((int64_t)o->store.C + 1)), dim3(256), 0,
+                       dim3(grid_for((int64_t)o->store.C + 1, 2048)),
+                       dim3(256), 0,
                        o->stream, D);
-    UHIP(o, hipGetLastError());
+    HIP_CHECK(o, hipGetLastError());
     unsigned long long n = 0;
-    UHIP(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
-                           o->stream));
-    UHIP(o, hipStreamSynchronize(o->stream));
-    if (ua_check_err(o)) return 1;
-    memset(out, 0, sizeof *out);
-    out->n_rows = (int64_t)n;
-    out->n_cols = ncols;
-    out->cols = (void **)calloc(ncols, sizeof(void *));
-    out->is_f64 = (int32_t *)calloc(ncols, sizeof(int32_t));
-    for (int i = 0; i < ncols; i++) {
-        out->cols[i] = malloc((size_t)(n ? n : 1) * 8);
-        if (n)
-            UHIP(o, hipMemcpyAsync(out->cols[i], o->d_out[i], (size_t)n * 8,
-                                   hipMemcpyDeviceToHost, o->stream));
-    }
-    UHIP(o, hipStreamSynchronize(o->stream));
-    return 0;
+    HIP_CHECK(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
+                                o->stream));
+    HIP_CHECK(o, hipStreamSynchronize(o->stream));
+    if (op_check_err(o, ua_err_msg)) return 1;
+    return op_out_alloc(o, out, (int64_t)n, ncols, __func__) ||
+           out_copy_cols(o, out, o->d_out, (int64_t)n);
 }
 
 API int arroyo_amd_updagg_restore(void *h, int32_t which,
@@ -1765,17 +1654,15 @@ API int arroyo_amd_updagg_restore(void *h, int32_t which,
     int64_t done = 0;
     while (done < n_rows) {
         int64_t take = n_rows - done;
-        if (take > o->stg_cap) take = o->stg_cap;
+        if (take > o->stg.cap) take = o->stg.cap;
         URestoreArgs R = {};
-        /* restore columns can exceed the input staging set: allocate ad hoc
-         * device buffers for this control-rate path */
-        std::vector<int64_t *> bufs;
+        /* restore columns can exceed the input staging set: ad hoc device
+         * buffers for this control-rate path, freed at the end of the
+         * iteration */
+        DevScratch tmp;
         for (int c = 0; c < n_cols; c++) {
             int64_t *d;
-            UHIP(o, hipMalloc((void **)&d, (size_t)take * 8));
-            UHIP(o, hipMemcpy(d, cols[c] + done, (size_t)take * 8,
-                              hipMemcpyHostToDevice));
-            bufs.push_back(d);
+            HIP_CHECK(o, tmp.upload(d, cols[c] + done, (size_t)take));
             R.cols[c] = d;
         }
         R.n_cols = n_cols;
@@ -1786,54 +1673,16 @@ API int arroyo_amd_updagg_restore(void *h, int32_t which,
         R.which = which;
         R.err = o->d_err;
         R.lastv = o->d_lastv;
-        hipLaunchKernelGGL(k_updagg_restore, dim3(ua_grid(take)), dim3(256),
+        hipLaunchKernelGGL(k_updagg_restore, dim3(grid_for(take, 2048)),
+                           dim3(256),
                            0, o->stream, R);
-        UHIP(o, hipGetLastError());
-        UHIP(o, hipStreamSynchronize(o->stream));
-        for (int64_t *d : bufs) hipFree(d);
+        HIP_CHECK(o, hipGetLastError());
+        HIP_CHECK(o, hipStreamSynchronize(o->stream));
         done += take;
     }
-    return ua_check_err(o);
+    return op_check_err(o, ua_err_msg);
 }
 
 API void arroyo_amd_updagg_destroy(void *h) {
-    GpuUpdAgg *o = (GpuUpdAgg *)h;
-    if (!o) return;
-    hipStreamSynchronize(o->stream);
-    hipFree(o->store.keys);
-    hipFree(o->store.epoch);
-    hipFree(o->store.rows);
-    hipFree(o->store.st);
-    hipFree(o->store.last);
-    hipFree(o->store.emitted);
-    hipFree(o->store.head);
-    hipFree(o->store.pool);
-    hipFree(o->store.pool_cur);
-    if (o->has_ord) {
-        hipFree(o->store.ord);
-        hipFree(o->d_arena);
-        hipFree(o->d_arena_cur);
-    }
-    int max_out = o->drain0_cols;
-    if (o->drain1_cols > max_out) max_out = o->drain1_cols;
-    if (o->out_cols > max_out) max_out = o->out_cols;
-    for (int i = 0; i < max_out; i++) hipFree(o->d_out[i]);
-    hipFree(o->d_n_out);
-    hipFree(o->d_err);
-    for (int c = 0; c < o->n_in_cols; c++) {
-        hipHostFree(o->stg_h[c]);
-        hipFree(o->stg_d[c]);
-    }
-    if (o->ns) {
-        hipFree(o->d_lastv);
-        hipFree(o->d_vmask);
-        hipFree(o->d_bm);
-        hipFree(o->d_nullcols);
-        for (int v = 0; v < o->cfg.n_value_cols; v++) {
-            hipHostFree(o->stg_vh[v]);
-            hipFree(o->stg_vd[v]);
-        }
-    }
-    hipStreamDestroy(o->stream);
-    delete o;
+    delete (GpuUpdAgg *)h;   /* ~OpBase drains the stream first */
 }

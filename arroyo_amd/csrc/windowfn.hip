@@ -21,32 +21,17 @@
  * the reference's most_active_driver_last_hour golden vector) by
  * tests/test_windowfn.py.
  */
-#include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <map>
-#include <vector>
 
-#include "../../include/arroyo_amd_types.h"
-
-#define API extern "C" __attribute__((visibility("default")))
+#include "op_common.h"
 
 namespace wfn {
 
-#define EMPTY_TAG (~0ULL)
 #define WERR_INSTANTS 1
 #define WERR_ROWS_CAP 2
 #define WERR_OUT_CAP  3
-
-__device__ inline uint64_t hash64(uint64_t x) {
-    x += 0x9e3779b97f4a7c15ULL;
-    x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ULL;
-    x = (x ^ (x >> 27)) * 0x94d049bb133111ebULL;
-    return x ^ (x >> 31);
-}
 
 __device__ inline uint64_t enc_asc(int64_t v) {
     return ((uint64_t)v) ^ 0x8000000000000000ULL;
@@ -198,9 +183,7 @@ k_wf_emit(WfEmitArgs E) {
 
 using namespace wfn;
 
-static char g_wf_err[256];
-
-struct GpuWindowFn {
+struct GpuWindowFn : OpBase {
     AmdWindowFnConfig cfg;
     int64_t seq;
     uint32_t I, cap;
@@ -220,31 +203,17 @@ struct GpuWindowFn {
     int64_t *d_slot_off;
     int64_t *d_out[14];
     unsigned long long *d_n_out;
-    int *d_err;
     int64_t out_cap;
-    int64_t *stg_h[12], *stg_d[12];
-    int64_t stg_cap;
+    Staging stg;
     std::vector<std::vector<int64_t>> host_out;
     int out_cols;
     int has_wm; uint64_t wm;
-    hipStream_t stream;
-    char err_msg[512];
 };
-
-#define WHIP(o, call)                                                         \
-    do {                                                                      \
-        hipError_t _e = (call);                                               \
-        if (_e != hipSuccess) {                                               \
-            snprintf((o)->err_msg, sizeof (o)->err_msg, "%s:%d hip: %s",      \
-                     __FILE__, __LINE__, hipGetErrorString(_e));              \
-            return 1;                                                         \
-        }                                                                     \
-    } while (0)
 
 API void *arroyo_amd_windowfn_create(const AmdWindowFnConfig *cfg) {
     if (!cfg || cfg->n_cols < 2 || cfg->n_cols > 12 || cfg->n_order < 1 ||
         cfg->n_order > 2 || cfg->part_col >= cfg->n_cols - 1) {
-        snprintf(g_wf_err, sizeof g_wf_err, "invalid windowfn config");
+        snprintf(g_create_err, sizeof g_create_err, "invalid windowfn config");
         return nullptr;
     }
     GpuWindowFn *o = new GpuWindowFn();
@@ -255,155 +224,66 @@ API void *arroyo_amd_windowfn_create(const AmdWindowFnConfig *cfg) {
     o->out_cols = cfg->n_cols + 1;
     o->out_cap = 1ll << (cfg->log2_out_cap ? cfg->log2_out_cap : 20);
     if (hipSetDevice(cfg->device) != hipSuccess) {
-        snprintf(g_wf_err, sizeof g_wf_err,
+        snprintf(g_create_err, sizeof g_create_err,
                  "hipSetDevice(%d) failed: no HIP device (no CPU fallback)",
                  cfg->device);
         delete o;
         return nullptr;
     }
-    hipError_t e;
-    auto fail = [&](const char *what, hipError_t e2) {
-        snprintf(g_wf_err, sizeof g_wf_err, "%s: %s", what,
-                 hipGetErrorString(e2));
-        delete o;
-        return nullptr;
-    };
-#define WALLOC(p, bytes)                                                      \
-    if ((e = hipMalloc((void **)&(p), (bytes))) != hipSuccess)                \
-        return fail(#p, e);
     size_t plane = (size_t)o->I * o->cap;
     o->scap = (int64_t)plane;
-    WALLOC(o->tag, (size_t)o->I * 8);
-    WALLOC(o->cursor, (size_t)o->I * 8);
-    WALLOC(o->planes, ((size_t)o->n_data + 1) * plane * 8);
-    WALLOC(o->scratch, ((size_t)o->n_data + 1) * plane * 8);
-    WALLOC(o->perm, plane * 8);
-    WALLOC(o->perm2, plane * 8);
-    WALLOC(o->keys, plane * 8);
-    WALLOC(o->keys2, plane * 8);
-    WALLOC(o->hf, plane * 8);
-    WALLOC(o->segid, plane * 8);
-    WALLOC(o->segstart, plane * 8);
-    WALLOC(o->d_slots, 64 * 4);
-    WALLOC(o->d_slot_off, 65 * 8);
+    OP_ALLOC(o, o->tag, (size_t)o->I * 8, 0xFF);
+    OP_ALLOC(o, o->cursor, (size_t)o->I * 8, 0);
+    OP_ALLOC(o, o->planes, ((size_t)o->n_data + 1) * plane * 8);
+    OP_ALLOC(o, o->scratch, ((size_t)o->n_data + 1) * plane * 8);
+    OP_ALLOC(o, o->perm, plane * 8);
+    OP_ALLOC(o, o->perm2, plane * 8);
+    OP_ALLOC(o, o->keys, plane * 8);
+    OP_ALLOC(o, o->keys2, plane * 8);
+    OP_ALLOC(o, o->hf, plane * 8);
+    OP_ALLOC(o, o->segid, plane * 8);
+    OP_ALLOC(o, o->segstart, plane * 8);
+    OP_ALLOC(o, o->d_slots, 64 * 4);
+    OP_ALLOC(o, o->d_slot_off, 65 * 8);
     for (int i = 0; i < o->out_cols; i++)
-        WALLOC(o->d_out[i], (size_t)o->out_cap * 8);
-    WALLOC(o->d_n_out, 8);
-    WALLOC(o->d_err, 4);
-#undef WALLOC
+        OP_ALLOC(o, o->d_out[i], (size_t)o->out_cap * 8);
+    OP_ALLOC(o, o->d_n_out, 8);
+    OP_ALLOC(o, o->d_err, 4, 0);
     /* hipCUB temp sizing (worst case n = plane) */
     o->cub_bytes = 0;
-    hipcub::DeviceRadixSort::SortPairs(
-        nullptr, o->cub_bytes, o->keys, o->keys2, o->perm, o->perm2,
-        (int)plane);
+    OP_TRY(o, "cub sort size",
+           hipcub::DeviceRadixSort::SortPairs(nullptr, o->cub_bytes, o->keys,
+                                              o->keys2, o->perm, o->perm2,
+                                              (int)plane));
     size_t scan_bytes = 0;
-    hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, o->hf, o->segid,
-                                     (int)plane);
+    OP_TRY(o, "cub scan size",
+           hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, o->hf,
+                                            o->segid, (int)plane));
     if (scan_bytes > o->cub_bytes) o->cub_bytes = scan_bytes;
-    if (hipMalloc(&o->cub_tmp, o->cub_bytes ? o->cub_bytes : 1) !=
-        hipSuccess) {
-        snprintf(g_wf_err, sizeof g_wf_err, "cub temp alloc failed");
-        delete o;
-        return nullptr;
-    }
-    hipMemset(o->tag, 0xFF, (size_t)o->I * 8);
-    hipMemset(o->cursor, 0, (size_t)o->I * 8);
-    hipMemset(o->d_err, 0, 4);
-    hipStreamCreate(&o->stream);
-    o->stg_cap = 1 << 20;
-    for (int c = 0; c < cfg->n_cols; c++) {
-        if (hipHostMalloc((void **)&o->stg_h[c], (size_t)o->stg_cap * 8) !=
-                hipSuccess ||
-            hipMalloc((void **)&o->stg_d[c], (size_t)o->stg_cap * 8) !=
-                hipSuccess) {
-            snprintf(g_wf_err, sizeof g_wf_err,
-                     "windowfn staging alloc failed");
-            delete o;
-            return nullptr;
-        }
-    }
+    OP_TRY_MSG(o, "cub temp alloc failed",
+               o->dev_alloc(o->cub_tmp, o->cub_bytes ? o->cub_bytes : 1));
+    OP_TRY(o, "hipStreamCreate", o->stream_create(&o->stream));
+    OP_TRY_MSG(o, "windowfn staging alloc failed",
+               o->stg.alloc(o, cfg->n_cols, 1 << 20));
     o->host_out.resize(o->out_cols);
     return o;
 }
 
 API const char *arroyo_amd_windowfn_last_error(void *h) {
-    return h ? ((GpuWindowFn *)h)->err_msg : g_wf_err;
+    return h ? ((GpuWindowFn *)h)->err_msg : g_create_err;
 }
 
-static int wf_check_err(GpuWindowFn *o) {
-    int e = 0;
-    WHIP(o, hipMemcpyAsync(&e, o->d_err, 4, hipMemcpyDeviceToHost,
-                           o->stream));
-    WHIP(o, hipStreamSynchronize(o->stream));
-    if (!e) return 0;
-    const char *msg =
-        e == WERR_INSTANTS ? "live-instant table full; raise instants"
-        : e == WERR_ROWS_CAP
-            ? "per-instant row buffer full; raise log2_rows_cap"
-        : e == WERR_OUT_CAP ? "output buffer full; raise log2_out_cap"
-                            : "device error";
-    snprintf(o->err_msg, sizeof o->err_msg, "%s", msg);
-    return 1;
+static const char *wf_err_msg(int e) {
+    return e == WERR_INSTANTS ? "live-instant table full; raise instants"
+           : e == WERR_ROWS_CAP
+               ? "per-instant row buffer full; raise log2_rows_cap"
+           : e == WERR_OUT_CAP ? "output buffer full; raise log2_out_cap"
+                               : "device error";
 }
 
-static int wf_grid(int64_t want) {
-    int64_t w = (want + 255) / 256;
-    return (int)(w > 2048 ? 2048 : (w < 1 ? 1 : w));
-}
-
-API int arroyo_amd_windowfn_process_batch(void *h, const int64_t *const *cols,
-                                          int32_t n_cols, int64_t n_rows) {
-    GpuWindowFn *o = (GpuWindowFn *)h;
-    if (n_cols != o->cfg.n_cols) {
-        snprintf(o->err_msg, sizeof o->err_msg, "expected %d cols, got %d",
-                 o->cfg.n_cols, n_cols);
-        return 1;
-    }
-    int64_t done = 0;
-    while (done < n_rows) {
-        int64_t take = n_rows - done;
-        if (take > o->stg_cap) take = o->stg_cap;
-        WfAppendArgs A = {};
-        for (int c = 0; c < n_cols; c++) {
-            memcpy(o->stg_h[c], cols[c] + done, (size_t)take * 8);
-            WHIP(o, hipMemcpyAsync(o->stg_d[c], o->stg_h[c],
-                                   (size_t)take * 8, hipMemcpyHostToDevice,
-                                   o->stream));
-            A.cols[c] = o->stg_d[c];
-        }
-        A.n_cols = n_cols;
-        A.n_rows = take;
-        A.tag = o->tag;
-        A.cursor = o->cursor;
-        A.planes = o->planes;
-        A.I = o->I;
-        A.cap = o->cap;
-        A.has_wm = o->has_wm;
-        A.wm = o->wm;
-        A.seq_base = o->seq;
-        o->seq += take;
-        A.err = o->d_err;
-        hipLaunchKernelGGL(k_wf_append, dim3(wf_grid(take)), dim3(256), 0,
-                           o->stream, A);
-        WHIP(o, hipGetLastError());
-        WHIP(o, hipStreamSynchronize(o->stream));
-        done += take;
-    }
-    return 0;
-}
-
-/* device-resident ingest: rows already in HBM append straight into the
- * instant table (no host staging); same arrival-sequence stamping */
-API int arroyo_amd_windowfn_process_batch_device(void *h,
-                                                 const int64_t *const *dcols,
-                                                 int32_t n_cols,
-                                                 int64_t n_rows) {
-    GpuWindowFn *o = (GpuWindowFn *)h;
-    if (n_cols != o->cfg.n_cols) {
-        snprintf(o->err_msg, sizeof o->err_msg, "expected %d cols, got %d",
-                 o->cfg.n_cols, n_cols);
-        return 1;
-    }
+/* append n_rows device rows to the instant table, stamping arrival order */
+static int wf_append(GpuWindowFn *o, const int64_t *const *dcols,
+                     int32_t n_cols, int64_t n_rows) {
     WfAppendArgs A = {};
     for (int c = 0; c < n_cols; c++) A.cols[c] = dcols[c];
     A.n_cols = n_cols;
@@ -418,9 +298,61 @@ API int arroyo_amd_windowfn_process_batch_device(void *h,
     A.seq_base = o->seq;
     o->seq += n_rows;
     A.err = o->d_err;
-    hipLaunchKernelGGL(k_wf_append, dim3(wf_grid(n_rows)), dim3(256), 0,
-                       o->stream, A);
-    WHIP(o, hipGetLastError());
+    hipLaunchKernelGGL(k_wf_append, dim3(grid_for(n_rows, 2048)), dim3(256),
+                       0, o->stream, A);
+    HIP_CHECK(o, hipGetLastError());
+    return 0;
+}
+
+static int wf_check_cols(GpuWindowFn *o, int32_t n_cols) {
+    if (n_cols == o->cfg.n_cols) return 0;
+    snprintf(o->err_msg, sizeof o->err_msg, "expected %d cols, got %d",
+             o->cfg.n_cols, n_cols);
+    return 1;
+}
+
+API int arroyo_amd_windowfn_process_batch(void *h, const int64_t *const *cols,
+                                          int32_t n_cols, int64_t n_rows) {
+    GpuWindowFn *o = (GpuWindowFn *)h;
+    if (wf_check_cols(o, n_cols)) return 1;
+    int64_t done = 0;
+    while (done < n_rows) {
+        int64_t take = n_rows - done;
+        if (take > o->stg.cap) take = o->stg.cap;
+        const int64_t *dcols[12];
+        if (o->stg.stage_chunk(o, cols, n_cols, done, take, dcols) ||
+            wf_append(o, dcols, n_cols, take))
+            return 1;
+        /* staging reused next iteration: wait for this append to finish */
+        HIP_CHECK(o, hipStreamSynchronize(o->stream));
+        done += take;
+    }
+    return 0;
+}
+
+/* device-resident ingest: rows already in HBM append straight into the
+ * instant table (no host staging); same arrival-sequence stamping */
+API int arroyo_amd_windowfn_process_batch_device(void *h,
+                                                 const int64_t *const *dcols,
+                                                 int32_t n_cols,
+                                                 int64_t n_rows) {
+    GpuWindowFn *o = (GpuWindowFn *)h;
+    if (wf_check_cols(o, n_cols)) return 1;
+    return wf_append(o, dcols, n_cols, n_rows);
+}
+
+/* one stable radix pass: reorder perm by scratch column `col` of the n
+ * gathered rows */
+static int wf_sort_pass(GpuWindowFn *o, int col, int desc, int64_t n) {
+    hipLaunchKernelGGL(k_wf_keys, dim3(grid_for(n, 2048)), dim3(256), 0,
+                       o->stream, o->scratch + (size_t)col * o->scap, o->perm,
+                       o->keys, n, desc);
+    HIP_CHECK(o, hipGetLastError());
+    size_t tmp = o->cub_bytes;
+    HIP_CHECK(o, hipcub::DeviceRadixSort::SortPairs(
+                     o->cub_tmp, tmp, o->keys, o->keys2, o->perm, o->perm2,
+                     (int)n, 0, 64, o->stream));
+    std::swap(o->perm, o->perm2);
     return 0;
 }
 
@@ -439,76 +371,45 @@ static int wf_fire(GpuWindowFn *o, uint64_t instant,
     int64_t n = off.back();
     if (n == 0) {
         for (uint32_t s : slots) {
-            WHIP(o, hipMemsetAsync(o->tag + s, 0xFF, 8, o->stream));
-            WHIP(o, hipMemsetAsync(o->cursor + s, 0, 8, o->stream));
+            HIP_CHECK(o, hipMemsetAsync(o->tag + s, 0xFF, 8, o->stream));
+            HIP_CHECK(o, hipMemsetAsync(o->cursor + s, 0, 8, o->stream));
         }
         return 0;
     }
-    WHIP(o, hipMemcpyAsync(o->d_slots, sl.data(), sl.size() * 4,
-                           hipMemcpyHostToDevice, o->stream));
-    WHIP(o, hipMemcpyAsync(o->d_slot_off, off.data(), off.size() * 8,
-                           hipMemcpyHostToDevice, o->stream));
-    hipLaunchKernelGGL(k_wf_gather, dim3(wf_grid(n)), dim3(256), 0,
+    HIP_CHECK(o, hipMemcpyAsync(o->d_slots, sl.data(), sl.size() * 4,
+                                hipMemcpyHostToDevice, o->stream));
+    HIP_CHECK(o, hipMemcpyAsync(o->d_slot_off, off.data(), off.size() * 8,
+                                hipMemcpyHostToDevice, o->stream));
+    hipLaunchKernelGGL(k_wf_gather, dim3(grid_for(n, 2048)), dim3(256), 0,
                        o->stream, o->planes, plane, o->cap, o->n_data + 1,
                        o->d_slots, o->d_slot_off, (int)sl.size(), n,
                        o->scratch, o->scap);
-    WHIP(o, hipGetLastError());
-    hipLaunchKernelGGL(k_wf_iota, dim3(wf_grid(n)), dim3(256), 0, o->stream,
+    HIP_CHECK(o, hipGetLastError());
+    hipLaunchKernelGGL(k_wf_iota, dim3(grid_for(n, 2048)),
+                       dim3(256), 0, o->stream,
                        o->perm, n);
-    WHIP(o, hipGetLastError());
+    HIP_CHECK(o, hipGetLastError());
     /* stable radix passes, least significant first: arrival seq (makes
      * ties deterministic = input order, like the reference's stable sort),
      * then ORDER BY cols, then the partition col */
-    {
-        hipLaunchKernelGGL(k_wf_keys, dim3(wf_grid(n)), dim3(256), 0,
-                           o->stream,
-                           o->scratch + (size_t)o->n_data * o->scap,
-                           o->perm, o->keys, n, 0);
-        WHIP(o, hipGetLastError());
-        size_t tmp = o->cub_bytes;
-        hipcub::DeviceRadixSort::SortPairs(o->cub_tmp, tmp, o->keys,
-                                           o->keys2, o->perm, o->perm2,
-                                           (int)n, 0, 64, o->stream);
-        std::swap(o->perm, o->perm2);
-    }
-    for (int j = c.n_order - 1; j >= 0; j--) {
-        hipLaunchKernelGGL(k_wf_keys, dim3(wf_grid(n)), dim3(256), 0,
-                           o->stream,
-                           o->scratch + (size_t)c.order_col[j] * o->scap,
-                           o->perm, o->keys, n, c.order_desc[j]);
-        WHIP(o, hipGetLastError());
-        size_t tmp = o->cub_bytes;
-        hipcub::DeviceRadixSort::SortPairs(o->cub_tmp, tmp, o->keys,
-                                           o->keys2, o->perm, o->perm2,
-                                           (int)n, 0, 64, o->stream);
-        std::swap(o->perm, o->perm2);
-    }
-    if (c.part_col >= 0) {
-        hipLaunchKernelGGL(k_wf_keys, dim3(wf_grid(n)), dim3(256), 0,
-                           o->stream,
-                           o->scratch + (size_t)c.part_col * o->scap,
-                           o->perm, o->keys, n, 0);
-        WHIP(o, hipGetLastError());
-        size_t tmp = o->cub_bytes;
-        hipcub::DeviceRadixSort::SortPairs(o->cub_tmp, tmp, o->keys,
-                                           o->keys2, o->perm, o->perm2,
-                                           (int)n, 0, 64, o->stream);
-        std::swap(o->perm, o->perm2);
-    }
-    hipLaunchKernelGGL(k_wf_heads, dim3(wf_grid(n)), dim3(256), 0, o->stream,
+    if (wf_sort_pass(o, o->n_data, 0, n)) return 1;
+    for (int j = c.n_order - 1; j >= 0; j--)
+        if (wf_sort_pass(o, c.order_col[j], c.order_desc[j], n)) return 1;
+    if (c.part_col >= 0 && wf_sort_pass(o, c.part_col, 0, n)) return 1;
+    hipLaunchKernelGGL(k_wf_heads, dim3(grid_for(n, 2048)),
+                       dim3(256), 0, o->stream,
                        c.part_col >= 0
                            ? o->scratch + (size_t)c.part_col * o->scap
                            : o->scratch,
                        o->perm, o->hf, n, c.part_col >= 0 ? 1 : 0);
-    WHIP(o, hipGetLastError());
-    {
-        size_t tmp = o->cub_bytes;
-        hipcub::DeviceScan::InclusiveSum(o->cub_tmp, tmp, o->hf, o->segid,
-                                         (int)n, o->stream);
-    }
-    hipLaunchKernelGGL(k_wf_segstart, dim3(wf_grid(n)), dim3(256), 0,
+    HIP_CHECK(o, hipGetLastError());
+    size_t tmp = o->cub_bytes;
+    HIP_CHECK(o, hipcub::DeviceScan::InclusiveSum(o->cub_tmp, tmp, o->hf,
+                                                  o->segid, (int)n,
+                                                  o->stream));
+    hipLaunchKernelGGL(k_wf_segstart, dim3(grid_for(n, 2048)), dim3(256), 0,
                        o->stream, o->hf, o->segid, o->segstart, n);
-    WHIP(o, hipGetLastError());
+    HIP_CHECK(o, hipGetLastError());
     WfEmitArgs E = {};
     E.scratch = o->scratch;
     E.scap = o->scap;
@@ -523,13 +424,14 @@ static int wf_fire(GpuWindowFn *o, uint64_t instant,
     E.n_out = o->d_n_out;
     E.out_cap = o->out_cap;
     E.err = o->d_err;
-    hipLaunchKernelGGL(k_wf_emit, dim3(wf_grid(n)), dim3(256), 0, o->stream,
+    hipLaunchKernelGGL(k_wf_emit, dim3(grid_for(n, 2048)),
+                       dim3(256), 0, o->stream,
                        E);
-    WHIP(o, hipGetLastError());
+    HIP_CHECK(o, hipGetLastError());
     /* retire the group's slots */
     for (uint32_t s : slots) {
-        WHIP(o, hipMemsetAsync(o->tag + s, 0xFF, 8, o->stream));
-        WHIP(o, hipMemsetAsync(o->cursor + s, 0, 8, o->stream));
+        HIP_CHECK(o, hipMemsetAsync(o->tag + s, 0xFF, 8, o->stream));
+        HIP_CHECK(o, hipMemsetAsync(o->cursor + s, 0, 8, o->stream));
     }
     return 0;
 }
@@ -537,41 +439,30 @@ static int wf_fire(GpuWindowFn *o, uint64_t instant,
 API int arroyo_amd_windowfn_handle_watermark(void *h, uint64_t wm,
                                              AmdOutBatch *out) {
     GpuWindowFn *o = (GpuWindowFn *)h;
-    if (wf_check_err(o)) return 1;
+    if (op_check_err(o, wf_err_msg)) return 1;
     o->has_wm = 1;
     o->wm = wm;
     std::vector<uint64_t> tags(o->I);
     std::vector<unsigned long long> cnt(o->I);
-    WHIP(o, hipMemcpyAsync(tags.data(), o->tag, (size_t)o->I * 8,
-                           hipMemcpyDeviceToHost, o->stream));
-    WHIP(o, hipMemcpyAsync(cnt.data(), o->cursor, (size_t)o->I * 8,
-                           hipMemcpyDeviceToHost, o->stream));
-    WHIP(o, hipStreamSynchronize(o->stream));
-    WHIP(o, hipMemsetAsync(o->d_n_out, 0, 8, o->stream));
+    HIP_CHECK(o, hipMemcpyAsync(tags.data(), o->tag, (size_t)o->I * 8,
+                                hipMemcpyDeviceToHost, o->stream));
+    HIP_CHECK(o, hipMemcpyAsync(cnt.data(), o->cursor, (size_t)o->I * 8,
+                                hipMemcpyDeviceToHost, o->stream));
+    HIP_CHECK(o, hipStreamSynchronize(o->stream));
+    HIP_CHECK(o, hipMemsetAsync(o->d_n_out, 0, 8, o->stream));
     std::map<uint64_t, std::vector<uint32_t>> fired;
     for (uint32_t s = 0; s < o->I; s++)
         if (tags[s] != EMPTY_TAG && tags[s] < wm) fired[tags[s]].push_back(s);
     for (auto &kv : fired)
         if (wf_fire(o, kv.first, kv.second, cnt)) return 1;
     unsigned long long n = 0;
-    WHIP(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
-                           o->stream));
-    WHIP(o, hipStreamSynchronize(o->stream));
-    if (wf_check_err(o)) return 1;
+    HIP_CHECK(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
+                                o->stream));
+    HIP_CHECK(o, hipStreamSynchronize(o->stream));
+    if (op_check_err(o, wf_err_msg)) return 1;
     if (out) {
-        memset(out, 0, sizeof *out);
-        out->n_rows = (int64_t)n;
-        out->n_cols = o->out_cols;
-        out->cols = (void **)calloc(o->out_cols, sizeof(void *));
-        out->is_f64 = (int32_t *)calloc(o->out_cols, sizeof(int32_t));
-        for (int i = 0; i < o->out_cols; i++) {
-            out->cols[i] = malloc((size_t)(n ? n : 1) * 8);
-            if (n)
-                WHIP(o, hipMemcpyAsync(out->cols[i], o->d_out[i],
-                                       (size_t)n * 8, hipMemcpyDeviceToHost,
-                                       o->stream));
-        }
-        WHIP(o, hipStreamSynchronize(o->stream));
+        if (op_out_alloc(o, out, (int64_t)n, o->out_cols, __func__)) return 1;
+        if (out_copy_cols(o, out, o->d_out, (int64_t)n)) return 1;
     }
     return 0;
 }
@@ -587,36 +478,30 @@ API int arroyo_amd_windowfn_restore(void *h, const int64_t *const *cols,
 
 API int arroyo_amd_windowfn_checkpoint_drain(void *h, AmdOutBatch *out) {
     GpuWindowFn *o = (GpuWindowFn *)h;
-    if (wf_check_err(o)) return 1;
+    if (op_check_err(o, wf_err_msg)) return 1;
     std::vector<uint64_t> tags(o->I);
     std::vector<unsigned long long> cnt(o->I);
-    WHIP(o, hipMemcpyAsync(tags.data(), o->tag, (size_t)o->I * 8,
-                           hipMemcpyDeviceToHost, o->stream));
-    WHIP(o, hipMemcpyAsync(cnt.data(), o->cursor, (size_t)o->I * 8,
-                           hipMemcpyDeviceToHost, o->stream));
-    WHIP(o, hipStreamSynchronize(o->stream));
+    HIP_CHECK(o, hipMemcpyAsync(tags.data(), o->tag, (size_t)o->I * 8,
+                                hipMemcpyDeviceToHost, o->stream));
+    HIP_CHECK(o, hipMemcpyAsync(cnt.data(), o->cursor, (size_t)o->I * 8,
+                                hipMemcpyDeviceToHost, o->stream));
+    HIP_CHECK(o, hipStreamSynchronize(o->stream));
     int ncols = o->cfg.n_cols;
     int64_t total = 0;
     for (uint32_t s = 0; s < o->I; s++)
         if (tags[s] != EMPTY_TAG) total += (int64_t)cnt[s];
-    memset(out, 0, sizeof *out);
-    out->n_rows = total;
-    out->n_cols = ncols;
-    out->cols = (void **)calloc(ncols, sizeof(void *));
-    out->is_f64 = (int32_t *)calloc(ncols, sizeof(int32_t));
-    for (int i = 0; i < ncols; i++)
-        out->cols[i] = malloc((size_t)(total ? total : 1) * 8);
+    if (op_out_alloc(o, out, total, ncols, __func__)) return 1;
     size_t plane = (size_t)o->I * o->cap;
     int64_t r = 0;
     for (uint32_t s = 0; s < o->I; s++) {
         if (tags[s] == EMPTY_TAG || cnt[s] == 0) continue;
         int64_t n = (int64_t)cnt[s];
         for (int cdx = 0; cdx < ncols - 1; cdx++)
-            WHIP(o, hipMemcpyAsync(
-                        (int64_t *)out->cols[cdx] + r,
-                        o->planes + (size_t)cdx * plane + (size_t)s * o->cap,
-                        (size_t)n * 8, hipMemcpyDeviceToHost, o->stream));
-        WHIP(o, hipStreamSynchronize(o->stream));
+            HIP_CHECK(o, hipMemcpyAsync(
+                    (int64_t *)out->cols[cdx] + r,
+                    o->planes + (size_t)cdx * plane + (size_t)s * o->cap,
+                    (size_t)n * 8, hipMemcpyDeviceToHost, o->stream));
+        HIP_CHECK(o, hipStreamSynchronize(o->stream));
         for (int64_t j = 0; j < n; j++)
             ((int64_t *)out->cols[ncols - 1])[r + j] = (int64_t)tags[s];
         r += n;
@@ -625,30 +510,5 @@ API int arroyo_amd_windowfn_checkpoint_drain(void *h, AmdOutBatch *out) {
 }
 
 API void arroyo_amd_windowfn_destroy(void *h) {
-    GpuWindowFn *o = (GpuWindowFn *)h;
-    if (!o) return;
-    hipStreamSynchronize(o->stream);
-    hipFree(o->tag);
-    hipFree(o->cursor);
-    hipFree(o->planes);
-    hipFree(o->scratch);
-    hipFree(o->perm);
-    hipFree(o->perm2);
-    hipFree(o->keys);
-    hipFree(o->keys2);
-    hipFree(o->hf);
-    hipFree(o->segid);
-    hipFree(o->segstart);
-    hipFree(o->cub_tmp);
-    hipFree(o->d_slots);
-    hipFree(o->d_slot_off);
-    for (int i = 0; i < o->out_cols; i++) hipFree(o->d_out[i]);
-    hipFree(o->d_n_out);
-    hipFree(o->d_err);
-    for (int c = 0; c < o->cfg.n_cols; c++) {
-        hipHostFree(o->stg_h[c]);
-        hipFree(o->stg_d[c]);
-    }
-    hipStreamDestroy(o->stream);
-    delete o;
+    delete (GpuWindowFn *)h;   /* ~OpBase drains the stream first */
 }

@@ -18,6 +18,8 @@ _SRCS = [os.path.join(_DIR, "csrc", f)
          for f in ("arroyo_amd.hip", "join.hip", "session.hip", "expjoin.hip",
                    "updagg.hip", "windowfn.hip", "mapop.hip", "strkey.hip",
                    "shuffle.hip")]
+# headers every source includes: editing one rebuilds the library
+_HDRS = [os.path.join(_DIR, "csrc", f) for f in ("op_common.h", "op_out.h")]
 
 _lib = None
 
@@ -28,7 +30,8 @@ HIPCC_CMD = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
 
 def build(force=False):
     if force or not os.path.exists(_SO) or \
-            os.path.getmtime(_SO) < max(os.path.getmtime(s) for s in _SRCS):
+            os.path.getmtime(_SO) < max(os.path.getmtime(s)
+                                        for s in _SRCS + _HDRS):
         proc = subprocess.run(HIPCC_CMD, cwd=_DIR,
                               capture_output=True, text=True)
         if proc.returncode != 0:

@@ -94,6 +94,32 @@ def test_gpu_multikey_matches_oracle(nk):
 
 
 @pytest.mark.gpu
+def test_gpu_multikey_widest_host_batch_matches_oracle():
+    """n_keys = 4 with n_value_cols = 4 is the widest input a config allows:
+    nine host columns through process_batch's staging (the other cases here
+    have six at most)."""
+    from arroyo_amd import gpu
+    n = 30_000
+    keys, val, ts = gen(n=n, seed=7, nk=4)
+    vals = [val, val * 3 + 1, 1000 - val, (val * 7) % 13]
+    kw = dict(n_value_cols=4,
+              aggs=[(cabi.COUNT, -1), (cabi.SUM, 0), (cabi.MIN, 1),
+                    (cabi.MAX, 2), (cabi.SUM, 3)])
+
+    def run(op):
+        outs = run_stream(
+            op, batches_from_columns([*keys, *vals, ts], 4096), NS)
+        got = concat_outputs(outs)
+        op.close()
+        return {tuple(int(c[r]) for c in got) for r in range(len(got[0]))}
+
+    g = run(gpu.make_op(cfg(4, **kw)))
+    w = run(oracle.make_op(cfg(4, **kw)))
+    assert len(w) > 100
+    assert g == w
+
+
+@pytest.mark.gpu
 def test_gpu_multikey_checkpoint_roundtrip():
     """Drain raw states (k key columns first), restore into a fresh op,
     finish the stream: outputs equal the uninterrupted run."""
