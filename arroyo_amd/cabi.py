@@ -1,9 +1,15 @@
-"""ctypes bindings for the arroyo-amd C ABI (include/arroyo_amd_types.h).
+"""ctypes bindings for the arroyo-amd C ABI (include/arroyo_amd.h).
 
 Generic over the implementing library: the product HIP library
 (libarroyo_amd.so, prefix ``arroyo_amd_``) and the CPU oracle
-(oracle/liboracle.so, prefix ``oracle_``) export the same function set; tests
-drive both through :class:`WindowOp` and compare.
+(oracle/liboracle.so, prefix ``oracle_``) export the same operator families;
+tests drive both through the wrapper classes below and compare.
+
+Layout of this file: the struct mirrors of include/arroyo_amd_types.h with
+their ``make_*_config`` helpers, then PROTOTYPES (every function of
+include/arroyo_amd.h, once), then ``_Handle`` and one thin wrapper class per
+family.  tests/test_cabi.py checks the mirrors and the table against the
+two headers.
 """
 import ctypes
 
@@ -68,101 +74,6 @@ def make_config(width_ns, slide_ns, aggs, n_keys=1, n_value_cols=0,
     return cfg
 
 
-def bind(lib, prefix):
-    fn = {}
-    g = lambda n: getattr(lib, prefix + n)
-    fn["create"] = g("create")
-    fn["create"].restype = ctypes.c_void_p
-    fn["create"].argtypes = [ctypes.POINTER(AmdWindowConfig)]
-    fn["process_batch"] = g("process_batch")
-    fn["process_batch"].restype = ctypes.c_int
-    fn["process_batch"].argtypes = [ctypes.c_void_p,
-                                    ctypes.POINTER(ctypes.c_void_p),
-                                    ctypes.c_int32, ctypes.c_int64]
-    fn["handle_watermark"] = g("handle_watermark")
-    fn["handle_watermark"].restype = ctypes.c_int
-    fn["handle_watermark"].argtypes = [ctypes.c_void_p, ctypes.c_uint64,
-                                       ctypes.POINTER(AmdOutBatch)]
-    try:
-        # batched variant (HIP library only; the oracle loops in Python)
-        fn["handle_watermarks"] = g("handle_watermarks")
-        fn["handle_watermarks"].restype = ctypes.c_int
-        fn["handle_watermarks"].argtypes = [
-            ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32,
-            ctypes.POINTER(AmdOutBatch)]
-        # epoch pipelining (HIP library only)
-        fn["set_filter_watermark"] = g("set_filter_watermark")
-        fn["set_filter_watermark"].restype = ctypes.c_int
-        fn["set_filter_watermark"].argtypes = [ctypes.c_void_p,
-                                               ctypes.c_uint64]
-        fn["mark_epoch"] = g("mark_epoch")
-        fn["mark_epoch"].restype = ctypes.c_int
-        fn["mark_epoch"].argtypes = [ctypes.c_void_p]
-        fn["handle_watermarks_epoch"] = g("handle_watermarks_epoch")
-        fn["handle_watermarks_epoch"].restype = ctypes.c_int
-        fn["handle_watermarks_epoch"].argtypes = [
-            ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32,
-            ctypes.POINTER(AmdOutBatch)]
-    except AttributeError:
-        pass
-    fn["checkpoint_drain"] = g("checkpoint_drain")
-    fn["checkpoint_drain"].restype = ctypes.c_int
-    fn["checkpoint_drain"].argtypes = [ctypes.c_void_p,
-                                       ctypes.POINTER(AmdOutBatch)]
-    fn["free_out"] = g("free_out")
-    fn["free_out"].argtypes = [ctypes.POINTER(AmdOutBatch)]
-    fn["destroy"] = g("destroy")
-    fn["destroy"].argtypes = [ctypes.c_void_p]
-    fn["last_error"] = g("last_error")
-    fn["last_error"].restype = ctypes.c_char_p
-    fn["last_error"].argtypes = [ctypes.c_void_p]
-    return fn
-
-
-def out_validity(out):
-    """Decode the Arrow validity bitmaps of an AmdOutBatch into per-column
-    numpy bool masks (None = column all-valid)."""
-    n = out.n_rows
-    masks = []
-    if not out.validity:
-        return [None] * out.n_cols
-    for i in range(out.n_cols):
-        bm = out.validity[i]
-        if not bm:
-            masks.append(None)
-            continue
-        nbytes = (n + 7) // 8
-        raw = np.frombuffer(
-            bytes(ctypes.cast(bm, ctypes.POINTER(
-                ctypes.c_uint8 * max(nbytes, 1))).contents),
-            dtype=np.uint8)
-        masks.append(np.unpackbits(raw, bitorder="little")[:n].astype(bool))
-    return masks
-
-
-def pack_validity(mask):
-    """Pack a bool mask into an Arrow validity bitmap (LSB bit order, bit
-    offset 0, (n + 7) // 8 bytes, padding bits clear): the inverse of
-    :func:`out_validity`."""
-    mask = np.ascontiguousarray(mask, dtype=bool)
-    return np.packbits(mask, bitorder="little")
-
-
-def _out_to_numpy(out):
-    """Copy an AmdOutBatch (host memory) into numpy arrays."""
-    n = out.n_rows
-    cols = []
-    for i in range(out.n_cols):
-        dt = np.float64 if out.is_f64[i] else np.int64
-        if n == 0:
-            cols.append(np.empty(0, dtype=dt))
-            continue
-        buf = ctypes.cast(out.cols[i], ctypes.POINTER(ctypes.c_int64 * n))
-        arr = np.frombuffer(bytearray(bytes(buf.contents)), dtype=dt).copy()
-        cols.append(arr)
-    return cols
-
-
 class AmdJoinConfig(ctypes.Structure):
     _fields_ = [
         ("n_keys", ctypes.c_int32),
@@ -194,200 +105,6 @@ def make_join_config(n_keys=1, n_left_vals=0, n_right_vals=0,
     cfg.emit_to_host = 1 if emit_to_host else 0
     cfg.join_type = join_type
     return cfg
-
-
-def bind_join(lib, prefix):
-    fn = {}
-    g = lambda n: getattr(lib, prefix + "join_" + n)
-    fn["create"] = g("create")
-    fn["create"].restype = ctypes.c_void_p
-    fn["create"].argtypes = [ctypes.POINTER(AmdJoinConfig)]
-    fn["process_batch"] = g("process_batch")
-    fn["process_batch"].restype = ctypes.c_int
-    fn["process_batch"].argtypes = [ctypes.c_void_p, ctypes.c_int32,
-                                    ctypes.POINTER(ctypes.c_void_p),
-                                    ctypes.c_int32, ctypes.c_int64]
-    fn["handle_watermark"] = g("handle_watermark")
-    fn["handle_watermark"].restype = ctypes.c_int
-    fn["handle_watermark"].argtypes = [ctypes.c_void_p, ctypes.c_uint64,
-                                       ctypes.POINTER(AmdOutBatch)]
-    fn["checkpoint_drain"] = g("checkpoint_drain")
-    fn["checkpoint_drain"].restype = ctypes.c_int
-    fn["checkpoint_drain"].argtypes = [ctypes.c_void_p, ctypes.c_int32,
-                                       ctypes.POINTER(AmdOutBatch)]
-    fn["free_out"] = getattr(lib, prefix + "free_out")
-    fn["free_out"].argtypes = [ctypes.POINTER(AmdOutBatch)]
-    fn["destroy"] = g("destroy")
-    fn["destroy"].argtypes = [ctypes.c_void_p]
-    fn["last_error"] = g("last_error")
-    fn["last_error"].restype = ctypes.c_char_p
-    fn["last_error"].argtypes = [ctypes.c_void_p]
-    return fn
-
-
-class JoinOp:
-    """One instant-join operator instance behind the C ABI (left = side 0,
-    right = side 1), mirroring InstantJoin's ArrowOperator surface
-    (crates/arroyo-worker/src/arrow/instant_join.rs)."""
-
-    LEFT, RIGHT = 0, 1
-
-    def __init__(self, lib, prefix, cfg):
-        self._fn = bind_join(lib, prefix)
-        self.cfg = cfg
-        self._h = self._fn["create"](ctypes.byref(cfg))
-        if not self._h:
-            raise RuntimeError(f"{prefix}join_create failed")
-
-    def process_batch(self, side, cols):
-        n_rows = len(cols[0]) if cols else 0
-        arr = (ctypes.c_void_p * len(cols))()
-        keep = []
-        for i, c in enumerate(cols):
-            c = np.ascontiguousarray(c, dtype=np.int64)
-            keep.append(c)
-            arr[i] = c.ctypes.data_as(ctypes.c_void_p).value
-        rc = self._fn["process_batch"](self._h, side, arr, len(cols), n_rows)
-        if rc != 0:
-            raise RuntimeError(self._fn["last_error"](self._h).decode())
-        return keep
-
-    def handle_watermark(self, wm):
-        out = AmdOutBatch()
-        rc = self._fn["handle_watermark"](self._h, wm, ctypes.byref(out))
-        if rc != 0:
-            raise RuntimeError(self._fn["last_error"](self._h).decode())
-        cols = _out_to_numpy(out)
-        self._fn["free_out"](ctypes.byref(out))
-        return cols
-
-    def checkpoint_drain(self, side):
-        out = AmdOutBatch()
-        rc = self._fn["checkpoint_drain"](self._h, side, ctypes.byref(out))
-        if rc != 0:
-            raise RuntimeError(self._fn["last_error"](self._h).decode())
-        cols = _out_to_numpy(out)
-        self._fn["free_out"](ctypes.byref(out))
-        return cols
-
-    def restore(self, side, cols):
-        """on_start re-processes drained batches (instant_join.rs:205-230)."""
-        if cols and len(cols[0]):
-            self.process_batch(side, cols)
-
-    def close(self):
-        if self._h:
-            self._fn["destroy"](self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class WindowOp:
-    """One window-aggregate operator instance behind the C ABI.
-
-    Mirrors the ArrowOperator calling convention
-    (crates/arroyo-operator/src/operator.rs:1144-1257): process_batch
-    ingests an owned batch; handle_watermark may emit result batches;
-    single-threaded per handle."""
-
-    def __init__(self, lib, prefix, cfg):
-        self._fn = bind(lib, prefix)
-        self.cfg = cfg
-        self._h = self._fn["create"](ctypes.byref(cfg))
-        if not self._h:
-            raise RuntimeError(f"{prefix}create failed (invalid config)")
-
-    def process_batch(self, cols):
-        """cols: list of np.int64 arrays [keys..., values..., _timestamp]."""
-        n_rows = len(cols[0]) if cols else 0
-        arr = (ctypes.c_void_p * len(cols))()
-        keep = []
-        for i, c in enumerate(cols):
-            c = np.ascontiguousarray(c, dtype=np.int64)
-            keep.append(c)
-            arr[i] = c.ctypes.data_as(ctypes.c_void_p).value
-        rc = self._fn["process_batch"](self._h, arr, len(cols), n_rows)
-        if rc != 0:
-            raise RuntimeError(self._fn["last_error"](self._h).decode())
-        return keep  # keep references alive through the call
-
-    def handle_watermark(self, wm):
-        out = AmdOutBatch()
-        rc = self._fn["handle_watermark"](self._h, wm, ctypes.byref(out))
-        if rc != 0:
-            raise RuntimeError(self._fn["last_error"](self._h).decode())
-        cols = _out_to_numpy(out)
-        self._fn["free_out"](ctypes.byref(out))
-        return cols
-
-    def handle_watermarks(self, wms):
-        """Batched watermarks with no rows between them: one device-status
-        round trip serves the whole group.  Semantically identical to
-        handle_watermark in order; returns all emissions concatenated.
-        Falls back to a Python loop where the library lacks the entry
-        point (the oracle)."""
-        if "handle_watermarks" not in self._fn:
-            outs = [self.handle_watermark(w) for w in wms]
-            outs = [o for o in outs if o and len(o[0])]
-            if not outs:
-                return []
-            return [np.concatenate([o[c] for o in outs])
-                    for c in range(len(outs[0]))]
-        out = AmdOutBatch()
-        arr = (ctypes.c_uint64 * len(wms))(*wms)
-        rc = self._fn["handle_watermarks"](self._h, arr, len(wms),
-                                           ctypes.byref(out))
-        if rc != 0:
-            raise RuntimeError(self._fn["last_error"](self._h).decode())
-        cols = _out_to_numpy(out)
-        self._fn["free_out"](ctypes.byref(out))
-        return cols
-
-    def set_filter_watermark(self, wm):
-        rc = self._fn["set_filter_watermark"](self._h, wm)
-        if rc != 0:
-            raise RuntimeError(self._fn["last_error"](self._h).decode())
-
-    def mark_epoch(self):
-        rc = self._fn["mark_epoch"](self._h)
-        if rc != 0:
-            raise RuntimeError(self._fn["last_error"](self._h).decode())
-
-    def handle_watermarks_epoch(self, wms):
-        out = AmdOutBatch()
-        arr = (ctypes.c_uint64 * len(wms))(*wms)
-        rc = self._fn["handle_watermarks_epoch"](self._h, arr, len(wms),
-                                                 ctypes.byref(out))
-        if rc != 0:
-            raise RuntimeError(self._fn["last_error"](self._h).decode())
-        cols = _out_to_numpy(out)
-        self._fn["free_out"](ctypes.byref(out))
-        return cols
-
-    def checkpoint_drain(self):
-        out = AmdOutBatch()
-        rc = self._fn["checkpoint_drain"](self._h, ctypes.byref(out))
-        if rc != 0:
-            raise RuntimeError(self._fn["last_error"](self._h).decode())
-        cols = _out_to_numpy(out)
-        self._fn["free_out"](ctypes.byref(out))
-        return cols
-
-    def close(self):
-        if self._h:
-            self._fn["destroy"](self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class AmdSessionConfig(ctypes.Structure):
@@ -468,261 +185,6 @@ def make_expjoin_config(ttl_ns, n_left_vals=0, n_right_vals=0,
     return cfg
 
 
-def _cols_to_ptrs(cols):
-    """Contiguous int64 copies + a void* array over them."""
-    keep = [np.ascontiguousarray(c, dtype=np.int64) for c in cols]
-    arr = (ctypes.c_void_p * len(keep))(
-        *[c.ctypes.data_as(ctypes.c_void_p).value for c in keep])
-    return keep, arr
-
-
-class SessionOp:
-    """One session-window aggregate operator behind the C ABI, mirroring
-    SessionAggregatingWindowFunc's ArrowOperator surface
-    (crates/arroyo-worker/src/arrow/session_aggregating_window.rs)."""
-
-    def __init__(self, lib, prefix, cfg):
-        p = prefix + "session_"
-        g = lambda n: getattr(lib, p + n)
-        self._fn = {}
-        self._fn["_lib_prefix"] = (lib, prefix)
-        self._fn["create"] = g("create")
-        self._fn["create"].restype = ctypes.c_void_p
-        self._fn["create"].argtypes = [ctypes.POINTER(AmdSessionConfig)]
-        self._fn["process_batch"] = g("process_batch")
-        self._fn["process_batch"].restype = ctypes.c_int
-        self._fn["process_batch"].argtypes = [
-            ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
-            ctypes.c_int64]
-        self._fn["handle_watermark"] = g("handle_watermark")
-        self._fn["handle_watermark"].restype = ctypes.c_int
-        self._fn["handle_watermark"].argtypes = [
-            ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(AmdOutBatch)]
-        self._fn["checkpoint_drain"] = g("checkpoint_drain")
-        self._fn["checkpoint_drain"].restype = ctypes.c_int
-        self._fn["checkpoint_drain"].argtypes = [
-            ctypes.c_void_p, ctypes.POINTER(AmdOutBatch)]
-        self._fn["restore"] = g("restore")
-        self._fn["restore"].restype = ctypes.c_int
-        self._fn["restore"].argtypes = [
-            ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
-            ctypes.c_int64]
-        self._fn["free_out"] = getattr(lib, prefix + "free_out")
-        self._fn["free_out"].argtypes = [ctypes.POINTER(AmdOutBatch)]
-        self._fn["destroy"] = g("destroy")
-        self._fn["destroy"].argtypes = [ctypes.c_void_p]
-        self._fn["last_error"] = g("last_error")
-        self._fn["last_error"].restype = ctypes.c_char_p
-        self._fn["last_error"].argtypes = [ctypes.c_void_p]
-        self.cfg = cfg
-        self._h = self._fn["create"](ctypes.byref(cfg))
-        if not self._h:
-            raise RuntimeError(f"{p}create failed: "
-                               f"{self._fn['last_error'](None)}")
-
-    def _check(self, rc):
-        if rc != 0:
-            raise RuntimeError(self._fn["last_error"](self._h).decode())
-
-    def process_batch(self, cols):
-        keep, arr = _cols_to_ptrs(cols)
-        n_rows = len(keep[0]) if keep else 0
-        self._check(self._fn["process_batch"](self._h, arr, len(keep),
-                                              n_rows))
-
-    def handle_watermark(self, wm):
-        out = AmdOutBatch()
-        self._check(self._fn["handle_watermark"](self._h, wm,
-                                                 ctypes.byref(out)))
-        cols = _out_to_numpy(out)
-        self._fn["free_out"](ctypes.byref(out))
-        return cols
-
-    def checkpoint_drain(self):
-        out = AmdOutBatch()
-        self._check(self._fn["checkpoint_drain"](self._h, ctypes.byref(out)))
-        cols = _out_to_numpy(out)
-        self._fn["free_out"](ctypes.byref(out))
-        return cols
-
-    def restore(self, cols):
-        keep, arr = _cols_to_ptrs(cols)
-        n_rows = len(keep[0]) if keep else 0
-        self._check(self._fn["restore"](self._h, arr, len(keep), n_rows))
-
-    def _bind_values(self):
-        # GPU-only extension (the oracle drains raw rows instead)
-        if "drain_values" not in self._fn:
-            g = self._fn["_lib_prefix"]
-            dv = getattr(g[0], g[1] + "session_drain_values")
-            dv.restype = ctypes.c_int
-            dv.argtypes = [ctypes.c_void_p, ctypes.POINTER(AmdOutBatch)]
-            rv = getattr(g[0], g[1] + "session_restore_values")
-            rv.restype = ctypes.c_int
-            rv.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
-                           ctypes.c_int32, ctypes.c_int64]
-            self._fn["drain_values"] = dv
-            self._fn["restore_values"] = rv
-
-    def drain_values(self):
-        self._bind_values()
-        out = AmdOutBatch()
-        self._check(self._fn["drain_values"](self._h, ctypes.byref(out)))
-        cols = _out_to_numpy(out)
-        self._fn["free_out"](ctypes.byref(out))
-        return cols
-
-    def restore_values(self, cols):
-        self._bind_values()
-        keep, arr = _cols_to_ptrs(cols)
-        n_rows = len(keep[0]) if keep else 0
-        self._check(self._fn["restore_values"](self._h, arr, len(keep),
-                                               n_rows))
-
-    def close(self):
-        if self._h:
-            self._fn["destroy"](self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class ExpJoinOp:
-    """One TTL'd (non-windowed) join operator behind the C ABI, mirroring
-    JoinWithExpiration's ArrowOperator surface
-    (crates/arroyo-worker/src/arrow/join_with_expiration.rs)."""
-
-    LEFT, RIGHT = 0, 1
-
-    def __init__(self, lib, prefix, cfg):
-        p = prefix + "expjoin_"
-        g = lambda n: getattr(lib, p + n)
-        self._fn = {}
-        self._fn["create"] = g("create")
-        self._fn["create"].restype = ctypes.c_void_p
-        self._fn["create"].argtypes = [ctypes.POINTER(AmdExpJoinConfig)]
-        self._fn["process_batch"] = g("process_batch")
-        self._fn["process_batch"].restype = ctypes.c_int
-        self._fn["process_batch"].argtypes = [
-            ctypes.c_void_p, ctypes.c_int32,
-            ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32, ctypes.c_int64,
-            ctypes.POINTER(AmdOutBatch)]
-        self._fn["handle_watermark"] = g("handle_watermark")
-        self._fn["handle_watermark"].restype = ctypes.c_int
-        self._fn["handle_watermark"].argtypes = [ctypes.c_void_p,
-                                                 ctypes.c_uint64]
-        self._fn["expire"] = g("expire")
-        self._fn["expire"].restype = ctypes.c_int
-        self._fn["expire"].argtypes = [ctypes.c_void_p]
-        self._fn["_lib_prefix"] = (lib, prefix)
-        self._fn["checkpoint_drain"] = g("checkpoint_drain")
-        self._fn["checkpoint_drain"].restype = ctypes.c_int
-        self._fn["checkpoint_drain"].argtypes = [
-            ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(AmdOutBatch)]
-        self._fn["restore"] = g("restore")
-        self._fn["restore"].restype = ctypes.c_int
-        self._fn["restore"].argtypes = [
-            ctypes.c_void_p, ctypes.c_int32,
-            ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32, ctypes.c_int64,
-            ctypes.c_int, ctypes.c_uint64]
-        self._fn["free_out"] = getattr(lib, prefix + "free_out")
-        self._fn["free_out"].argtypes = [ctypes.POINTER(AmdOutBatch)]
-        self._fn["destroy"] = g("destroy")
-        self._fn["destroy"].argtypes = [ctypes.c_void_p]
-        self._fn["last_error"] = g("last_error")
-        self._fn["last_error"].restype = ctypes.c_char_p
-        self._fn["last_error"].argtypes = [ctypes.c_void_p]
-        self.cfg = cfg
-        self._h = self._fn["create"](ctypes.byref(cfg))
-        if not self._h:
-            raise RuntimeError(f"{p}create failed: "
-                               f"{self._fn['last_error'](None)}")
-
-    def _check(self, rc):
-        if rc != 0:
-            raise RuntimeError(self._fn["last_error"](self._h).decode())
-
-    def process_batch(self, side, cols):
-        keep, arr = _cols_to_ptrs(cols)
-        n_rows = len(keep[0]) if keep else 0
-        out = AmdOutBatch()
-        self._check(self._fn["process_batch"](self._h, side, arr, len(keep),
-                                              n_rows, ctypes.byref(out)))
-        res = _out_to_numpy(out)
-        self._fn["free_out"](ctypes.byref(out))
-        return res
-
-    def handle_watermark(self, wm):
-        self._check(self._fn["handle_watermark"](self._h, wm))
-
-    def _bind_device(self):
-        # GPU-only extension (the oracle has no device-resident path)
-        if "process_batch_device" not in self._fn:
-            lib, prefix = self._fn["_lib_prefix"]
-            pd = getattr(lib, prefix + "expjoin_process_batch_device")
-            pd.restype = ctypes.c_int
-            pd.argtypes = [ctypes.c_void_p, ctypes.c_int32,
-                           ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
-                           ctypes.c_int64]
-            co = getattr(lib, prefix + "expjoin_collect")
-            co.restype = ctypes.c_int
-            co.argtypes = [ctypes.c_void_p, ctypes.POINTER(AmdOutBatch)]
-            self._fn["process_batch_device"] = pd
-            self._fn["collect"] = co
-
-    def process_batch_device(self, side, dptrs, n_rows):
-        """Device-resident ingest: dptrs are raw device addresses of the
-        same [key, vals..., ts] columns process_batch takes.  Matches
-        accumulate on the device until collect()."""
-        self._bind_device()
-        arr = (ctypes.c_void_p * len(dptrs))(*dptrs)
-        self._check(self._fn["process_batch_device"](
-            self._h, side, arr, len(dptrs), n_rows))
-
-    def collect(self):
-        """Drain device-accumulated match rows to host numpy columns."""
-        self._bind_device()
-        out = AmdOutBatch()
-        self._check(self._fn["collect"](self._h, ctypes.byref(out)))
-        res = _out_to_numpy(out)
-        self._fn["free_out"](ctypes.byref(out))
-        return res
-
-    def expire(self):
-        self._check(self._fn["expire"](self._h))
-
-    def checkpoint_drain(self, side):
-        out = AmdOutBatch()
-        self._check(self._fn["checkpoint_drain"](self._h, side,
-                                                 ctypes.byref(out)))
-        cols = _out_to_numpy(out)
-        self._fn["free_out"](ctypes.byref(out))
-        return cols
-
-    def restore(self, side, cols, watermark=None):
-        keep, arr = _cols_to_ptrs(cols)
-        n_rows = len(keep[0]) if keep else 0
-        self._check(self._fn["restore"](
-            self._h, side, arr, len(keep), n_rows,
-            1 if watermark is not None else 0,
-            watermark if watermark is not None else 0))
-
-    def close(self):
-        if self._h:
-            self._fn["destroy"](self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
 COUNT_DISTINCT = 5
 STDDEV = 6
 STDDEV_POP = 7
@@ -789,196 +251,6 @@ def make_updagg_config(aggs, n_keys=1, n_value_cols=0, log2_capacity=16,
     return cfg
 
 
-class UpdAggOp:
-    """One updating (non-windowed) aggregate operator behind the C ABI,
-    mirroring IncrementalAggregatingFunc's ArrowOperator surface
-    (crates/arroyo-worker/src/arrow/incremental_aggregator.rs)."""
-
-    def __init__(self, lib, prefix, cfg):
-        p = prefix + "updagg_"
-        g = lambda n: getattr(lib, p + n)
-        self._fn = {}
-        self._fn["create"] = g("create")
-        self._fn["create"].restype = ctypes.c_void_p
-        self._fn["create"].argtypes = [ctypes.POINTER(AmdUpdatingConfig)]
-        self._fn["process_batch"] = g("process_batch")
-        self._fn["process_batch"].restype = ctypes.c_int
-        self._fn["process_batch"].argtypes = [
-            ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
-            ctypes.c_int64]
-        self._fn["flush"] = g("flush")
-        self._fn["flush"].restype = ctypes.c_int
-        self._fn["flush"].argtypes = [ctypes.c_void_p,
-                                      ctypes.POINTER(AmdOutBatch)]
-        self._fn["expire"] = g("expire")
-        self._fn["expire"].restype = ctypes.c_int
-        self._fn["expire"].argtypes = [ctypes.c_void_p, ctypes.c_int64,
-                                       ctypes.POINTER(AmdOutBatch)]
-        self._fn["_lib_prefix"] = (lib, prefix)
-        self._fn["checkpoint_drain"] = g("checkpoint_drain")
-        self._fn["checkpoint_drain"].restype = ctypes.c_int
-        self._fn["checkpoint_drain"].argtypes = [
-            ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(AmdOutBatch)]
-        self._fn["restore"] = g("restore")
-        self._fn["restore"].restype = ctypes.c_int
-        self._fn["restore"].argtypes = [
-            ctypes.c_void_p, ctypes.c_int32,
-            ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32, ctypes.c_int64]
-        self._fn["free_out"] = getattr(lib, prefix + "free_out")
-        self._fn["free_out"].argtypes = [ctypes.POINTER(AmdOutBatch)]
-        self._fn["destroy"] = g("destroy")
-        self._fn["destroy"].argtypes = [ctypes.c_void_p]
-        self._fn["last_error"] = g("last_error")
-        self._fn["last_error"].restype = ctypes.c_char_p
-        self._fn["last_error"].argtypes = [ctypes.c_void_p]
-        self.cfg = cfg
-        self._h = self._fn["create"](ctypes.byref(cfg))
-        if not self._h:
-            raise RuntimeError(
-                f"{p}create failed: "
-                f"{self._fn['last_error'](None).decode()}")
-
-    def _check(self, rc):
-        if rc != 0:
-            raise RuntimeError(self._fn["last_error"](self._h).decode())
-
-    def process_batch(self, cols):
-        keep, arr = _cols_to_ptrs(cols)
-        n_rows = len(keep[0]) if keep else 0
-        self._check(self._fn["process_batch"](self._h, arr, len(keep),
-                                              n_rows))
-
-    def process_batch_device(self, dptrs, n_rows):
-        """Device-resident ingest (GPU-only extension): dptrs are raw
-        device addresses of the [keys..., vals..., is_retract] columns."""
-        if "process_batch_device" not in self._fn:
-            lib, prefix = self._fn["_lib_prefix"]
-            pd = getattr(lib, prefix + "updagg_process_batch_device")
-            pd.restype = ctypes.c_int
-            pd.argtypes = [ctypes.c_void_p,
-                           ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
-                           ctypes.c_int64]
-            self._fn["process_batch_device"] = pd
-        arr = (ctypes.c_void_p * len(dptrs))(*dptrs)
-        self._check(self._fn["process_batch_device"](self._h, arr,
-                                                     len(dptrs), n_rows))
-
-    def _bind_nullable(self, name):
-        """Nullable ingest is a GPU-library extension (the C oracle has no
-        NULLs): bound on first use so oracle-backed ops still construct."""
-        if name not in self._fn:
-            lib, prefix = self._fn["_lib_prefix"]
-            f = getattr(lib, prefix + "updagg_" + name)
-            f.restype = ctypes.c_int
-            f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
-                          ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
-                          ctypes.c_int64]
-            self._fn[name] = f
-        return self._fn[name]
-
-    def process_batch_nullable(self, cols, valid):
-        """cols as for process_batch; valid is None (everything valid) or a
-        list parallel to cols whose entries are None (column all valid) or
-        a bool array (True = non-null)."""
-        f = self._bind_nullable("process_batch_nullable")
-        keep, arr = _cols_to_ptrs(cols)
-        n_rows = len(keep[0]) if keep else 0
-        varr, vkeep = None, []
-        if valid is not None:
-            if len(valid) != len(keep):
-                raise ValueError(
-                    f"valid has {len(valid)} entries for {len(keep)} cols")
-            ptrs = []
-            for m in valid:
-                if m is None:
-                    ptrs.append(None)
-                    continue
-                if len(m) != n_rows:
-                    raise ValueError("validity mask length != n_rows")
-                bm = pack_validity(m)
-                if len(bm) == 0:
-                    bm = np.zeros(1, dtype=np.uint8)
-                vkeep.append(bm)
-                ptrs.append(bm.ctypes.data_as(ctypes.c_void_p).value)
-            varr = (ctypes.c_void_p * len(ptrs))(*ptrs)
-        self._check(f(self._h, arr, varr, len(keep), n_rows))
-
-    def process_batch_nullable_device(self, dptrs, dvalid_ptrs, n_rows):
-        """Device-resident nullable ingest: dptrs as for
-        process_batch_device; dvalid_ptrs is None or a list parallel to
-        dptrs of None / raw device addresses of Arrow validity bitmaps
-        (8-byte aligned, padded to a multiple of 8 bytes)."""
-        f = self._bind_nullable("process_batch_nullable_device")
-        arr = (ctypes.c_void_p * len(dptrs))(*dptrs)
-        varr = None
-        if dvalid_ptrs is not None:
-            if len(dvalid_ptrs) != len(dptrs):
-                raise ValueError(
-                    f"dvalid_ptrs has {len(dvalid_ptrs)} entries for "
-                    f"{len(dptrs)} cols")
-            varr = (ctypes.c_void_p * len(dvalid_ptrs))(*dvalid_ptrs)
-        self._check(f(self._h, arr, varr, len(dptrs), n_rows))
-
-    def _take_out(self, out, with_validity):
-        cols = _out_to_numpy(out)
-        masks = out_validity(out) if with_validity else None
-        self._fn["free_out"](ctypes.byref(out))
-        if not with_validity:
-            return cols
-        n = len(cols[0]) if cols else 0
-        masks = [np.ones(n, dtype=bool) if m is None else m for m in masks]
-        return cols, masks
-
-    def flush(self):
-        out = AmdOutBatch()
-        self._check(self._fn["flush"](self._h, ctypes.byref(out)))
-        return self._take_out(out, False)
-
-    def flush_with_validity(self):
-        """flush() plus the per-column validity as bool masks (all True for
-        a column without a bitmap): returns (cols, masks)."""
-        out = AmdOutBatch()
-        self._check(self._fn["flush"](self._h, ctypes.byref(out)))
-        return self._take_out(out, True)
-
-    def expire(self, idle_flushes):
-        out = AmdOutBatch()
-        self._check(self._fn["expire"](self._h, idle_flushes,
-                                       ctypes.byref(out)))
-        return self._take_out(out, False)
-
-    def expire_with_validity(self, idle_flushes):
-        out = AmdOutBatch()
-        self._check(self._fn["expire"](self._h, idle_flushes,
-                                       ctypes.byref(out)))
-        return self._take_out(out, True)
-
-    def checkpoint_drain(self, which):
-        out = AmdOutBatch()
-        self._check(self._fn["checkpoint_drain"](self._h, which,
-                                                 ctypes.byref(out)))
-        cols = _out_to_numpy(out)
-        self._fn["free_out"](ctypes.byref(out))
-        return cols
-
-    def restore(self, which, cols):
-        keep, arr = _cols_to_ptrs(cols)
-        n_rows = len(keep[0]) if keep else 0
-        self._check(self._fn["restore"](self._h, which, arr, len(keep),
-                                        n_rows))
-
-    def close(self):
-        if self._h:
-            self._fn["destroy"](self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
 class AmdWindowFnConfig(ctypes.Structure):
     _fields_ = [
         ("n_cols", ctypes.c_int32),
@@ -1013,111 +285,6 @@ def make_windowfn_config(n_cols, part_col, order, limit=0, log2_rows_cap=15,
     cfg.device = device
     cfg.emit_to_host = 1 if emit_to_host else 0
     return cfg
-
-
-class WindowFnOp:
-    """One ROW_NUMBER window-function operator behind the C ABI, mirroring
-    WindowFunctionOperator's ArrowOperator surface
-    (crates/arroyo-worker/src/arrow/window_fn.rs)."""
-
-    def __init__(self, lib, prefix, cfg):
-        p = prefix + "windowfn_"
-        g = lambda n: getattr(lib, p + n)
-        self._fn = {}
-        self._fn["create"] = g("create")
-        self._fn["create"].restype = ctypes.c_void_p
-        self._fn["create"].argtypes = [ctypes.POINTER(AmdWindowFnConfig)]
-        self._fn["process_batch"] = g("process_batch")
-        self._fn["process_batch"].restype = ctypes.c_int
-        self._fn["process_batch"].argtypes = [
-            ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
-            ctypes.c_int64]
-        self._fn["handle_watermark"] = g("handle_watermark")
-        self._fn["handle_watermark"].restype = ctypes.c_int
-        self._fn["handle_watermark"].argtypes = [
-            ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(AmdOutBatch)]
-        self._fn["restore"] = g("restore")
-        self._fn["restore"].restype = ctypes.c_int
-        self._fn["restore"].argtypes = [
-            ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
-            ctypes.c_int64]
-        self._fn["checkpoint_drain"] = g("checkpoint_drain")
-        self._fn["checkpoint_drain"].restype = ctypes.c_int
-        self._fn["checkpoint_drain"].argtypes = [
-            ctypes.c_void_p, ctypes.POINTER(AmdOutBatch)]
-        self._fn["free_out"] = getattr(lib, prefix + "free_out")
-        self._fn["free_out"].argtypes = [ctypes.POINTER(AmdOutBatch)]
-        self._fn["destroy"] = g("destroy")
-        self._fn["destroy"].argtypes = [ctypes.c_void_p]
-        self._fn["last_error"] = g("last_error")
-        self._fn["last_error"].restype = ctypes.c_char_p
-        self._fn["last_error"].argtypes = [ctypes.c_void_p]
-        self._fn["_lib_prefix"] = (lib, prefix)
-        self.cfg = cfg
-        self._h = self._fn["create"](ctypes.byref(cfg))
-        if not self._h:
-            raise RuntimeError(
-                f"{p}create failed: "
-                f"{self._fn['last_error'](None).decode()}")
-
-    def _check(self, rc):
-        if rc != 0:
-            raise RuntimeError(self._fn["last_error"](self._h).decode())
-
-    def process_batch(self, cols):
-        keep, arr = _cols_to_ptrs(cols)
-        self._check(self._fn["process_batch"](
-            self._h, arr, len(keep), len(keep[0]) if keep else 0))
-
-    def process_batch_device(self, dptrs, n_rows):
-        """Device-resident ingest (GPU-only extension): dptrs are raw
-        device addresses of the same columns process_batch takes."""
-        if "process_batch_device" not in self._fn:
-            lib, prefix = self._fn["_lib_prefix"]
-            pd = getattr(lib, prefix + "windowfn_process_batch_device")
-            pd.restype = ctypes.c_int
-            pd.argtypes = [ctypes.c_void_p,
-                           ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
-                           ctypes.c_int64]
-            self._fn["process_batch_device"] = pd
-        arr = (ctypes.c_void_p * len(dptrs))(*dptrs)
-        self._check(self._fn["process_batch_device"](self._h, arr,
-                                                     len(dptrs), n_rows))
-
-    def restore(self, cols):
-        keep, arr = _cols_to_ptrs(cols)
-        self._check(self._fn["restore"](
-            self._h, arr, len(keep), len(keep[0]) if keep else 0))
-
-    def handle_watermark(self, wm):
-        out = AmdOutBatch()
-        self._check(self._fn["handle_watermark"](self._h, wm,
-                                                 ctypes.byref(out)))
-        cols = _out_to_numpy(out)
-        self._fn["free_out"](ctypes.byref(out))
-        return cols
-
-    def checkpoint_drain(self):
-        out = AmdOutBatch()
-        self._check(self._fn["checkpoint_drain"](self._h, ctypes.byref(out)))
-        cols = _out_to_numpy(out)
-        self._fn["free_out"](ctypes.byref(out))
-        return cols
-
-    def restore(self, cols):
-        if cols and len(cols[0]):
-            self.process_batch(cols)
-
-    def close(self):
-        if self._h:
-            self._fn["destroy"](self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 MOP_CONST, MOP_ADD, MOP_SUB, MOP_MUL, MOP_DIV, MOP_MOD = range(6)
@@ -1174,86 +341,6 @@ def make_map_config(n_in_cols, prog, out_reg, out_is_f64=None,
     return cfg
 
 
-class MapOp:
-    """One stateless map/filter/projection operator behind the C ABI,
-    mirroring the expression operators' ArrowOperator surface
-    (crates/arroyo-worker/src/arrow/mod.rs:48-243)."""
-
-    def __init__(self, lib, prefix, cfg):
-        p = prefix + "map_"
-        g = lambda n: getattr(lib, p + n)
-        self._fn = {}
-        self._fn["create"] = g("create")
-        self._fn["create"].restype = ctypes.c_void_p
-        self._fn["create"].argtypes = [ctypes.POINTER(AmdMapConfig)]
-        self._fn["process_batch"] = g("process_batch")
-        self._fn["process_batch"].restype = ctypes.c_int
-        self._fn["process_batch"].argtypes = [
-            ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
-            ctypes.c_int64, ctypes.POINTER(AmdOutBatch)]
-        self._fn["free_out"] = getattr(lib, prefix + "free_out")
-        self._fn["free_out"].argtypes = [ctypes.POINTER(AmdOutBatch)]
-        self._fn["destroy"] = g("destroy")
-        self._fn["destroy"].argtypes = [ctypes.c_void_p]
-        self._fn["last_error"] = g("last_error")
-        self._fn["last_error"].restype = ctypes.c_char_p
-        self._fn["last_error"].argtypes = [ctypes.c_void_p]
-        self._fn["_lib_prefix"] = (lib, prefix)
-        self.cfg = cfg
-        self._h = self._fn["create"](ctypes.byref(cfg))
-        if not self._h:
-            raise RuntimeError(
-                f"{p}create failed: "
-                f"{self._fn['last_error'](None).decode()}")
-
-    def process_batch_device(self, dptrs, n_rows):
-        """Device-resident map/filter (GPU-only extension): input device
-        addresses in, (device output addresses, surviving row count) out.
-        The returned addresses are owned by the operator and valid until
-        the next process_batch* call."""
-        if "process_batch_device" not in self._fn:
-            lib, prefix = self._fn["_lib_prefix"]
-            pd = getattr(lib, prefix + "map_process_batch_device")
-            pd.restype = ctypes.c_int
-            pd.argtypes = [ctypes.c_void_p,
-                           ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
-                           ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p),
-                           ctypes.POINTER(ctypes.c_int64)]
-            self._fn["process_batch_device"] = pd
-        arr = (ctypes.c_void_p * len(dptrs))(*dptrs)
-        outp = (ctypes.c_void_p * self.cfg.n_out)()
-        n_out = ctypes.c_int64(0)
-        rc = self._fn["process_batch_device"](self._h, arr, len(dptrs),
-                                              n_rows, outp,
-                                              ctypes.byref(n_out))
-        if rc != 0:
-            raise RuntimeError(self._fn["last_error"](self._h).decode())
-        return [outp[i] for i in range(self.cfg.n_out)], int(n_out.value)
-
-    def process_batch(self, cols):
-        keep, arr = _cols_to_ptrs(cols)
-        out = AmdOutBatch()
-        rc = self._fn["process_batch"](self._h, arr, len(keep),
-                                       len(keep[0]) if keep else 0,
-                                       ctypes.byref(out))
-        if rc != 0:
-            raise RuntimeError(self._fn["last_error"](self._h).decode())
-        res = _out_to_numpy(out)
-        self._fn["free_out"](ctypes.byref(out))
-        return res
-
-    def close(self):
-        if self._h:
-            self._fn["destroy"](self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
 # ---- device string-key dictionary (arroyo_amd_strkey_*) -------------------
 
 class AmdStrKeyConfig(ctypes.Structure):
@@ -1282,171 +369,6 @@ def make_strkey_config(log2_capacity=16, arena_bytes=1 << 24, hash_bits=0,
     cfg.arena_bytes = arena_bytes
     cfg.hash_bits = hash_bits
     return cfg
-
-
-def strings_to_arrow(strings):
-    """list[bytes | str] -> (int32 offsets [n + 1], uint8 data): the two
-    buffers of an Arrow Utf8 array.  str items are encoded as UTF-8."""
-    raw = [s.encode("utf-8") if isinstance(s, str) else bytes(s)
-           for s in strings]
-    lens = np.fromiter((len(b) for b in raw), dtype=np.int64, count=len(raw))
-    offsets = np.zeros(len(raw) + 1, dtype=np.int64)
-    np.cumsum(lens, out=offsets[1:])
-    if offsets[-1] > np.iinfo(np.int32).max:
-        raise ValueError("strings exceed the int32 offset range of Utf8")
-    data = np.frombuffer(b"".join(raw), dtype=np.uint8).copy()
-    return offsets.astype(np.int32), data
-
-
-def arrow_to_strings(offsets, data):
-    """(offsets, data) -> list[bytes]; honours a non-zero offsets[0]."""
-    buf = np.ascontiguousarray(data, dtype=np.uint8).tobytes()
-    off = [int(o) for o in offsets]
-    return [buf[off[i]:off[i + 1]] for i in range(len(off) - 1)]
-
-
-def _strbatch_to_numpy(out):
-    n = int(out.n_rows)
-    ids = np.ctypeslib.as_array(out.ids, shape=(n,)).copy() if n else \
-        np.zeros(0, dtype=np.int64)
-    offsets = np.ctypeslib.as_array(out.offsets, shape=(n + 1,)).copy()
-    total = int(offsets[-1])
-    data = np.ctypeslib.as_array(out.data, shape=(total,)).copy() if total \
-        else np.zeros(0, dtype=np.uint8)
-    return ids, offsets, data
-
-
-class StrKeyDict:
-    """Device-resident string interner behind the C ABI: Arrow Utf8 key
-    columns in, stable non-negative int64 ids out (and back).  Share one
-    instance between every operator that must agree on the ids."""
-
-    def __init__(self, lib, prefix, cfg):
-        p = prefix + "strkey_"
-        g = lambda n: getattr(lib, p + n)
-        vp, i64 = ctypes.c_void_p, ctypes.c_int64
-        fn = {}
-        fn["create"] = g("create")
-        fn["create"].restype = vp
-        fn["create"].argtypes = [ctypes.POINTER(AmdStrKeyConfig)]
-        for name, args in (
-                ("encode", [vp, vp, vp, i64, vp, vp]),
-                ("encode_device", [vp, vp, vp, i64, vp, vp]),
-                ("decode", [vp, vp, i64, ctypes.POINTER(AmdStrBatch)]),
-                ("count", [vp, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
-                ("checkpoint_drain", [vp, ctypes.POINTER(AmdStrBatch)]),
-                ("restore", [vp, vp, vp, vp, i64]),
-                ("profile", [vp, ctypes.c_int,
-                             ctypes.POINTER(ctypes.c_double)])):
-            fn[name] = g(name)
-            fn[name].restype = ctypes.c_int
-            fn[name].argtypes = args
-        fn["free_out"] = g("free_out")
-        fn["free_out"].restype = None
-        fn["free_out"].argtypes = [ctypes.POINTER(AmdStrBatch)]
-        fn["destroy"] = g("destroy")
-        fn["destroy"].restype = None
-        fn["destroy"].argtypes = [vp]
-        fn["last_error"] = g("last_error")
-        fn["last_error"].restype = ctypes.c_char_p
-        fn["last_error"].argtypes = [vp]
-        self._fn = fn
-        self.cfg = cfg
-        self._h = fn["create"](ctypes.byref(cfg))
-        if not self._h:
-            raise RuntimeError(
-                f"{p}create failed: {fn['last_error'](None).decode()}")
-
-    def _check(self, rc):
-        if rc != 0:
-            raise RuntimeError(self._fn["last_error"](self._h).decode())
-
-    @staticmethod
-    def _arrow(offsets, data):
-        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
-        data = np.ascontiguousarray(data, dtype=np.uint8)
-        if len(offsets) < 1:
-            raise ValueError("offsets needs n_rows + 1 entries")
-        return offsets, data
-
-    def encode(self, offsets, data, with_hashes=False):
-        """Host Arrow buffers -> int64 ids (and uint64 content hashes when
-        with_hashes)."""
-        offsets, data = self._arrow(offsets, data)
-        n = len(offsets) - 1
-        ids = np.empty(n, dtype=np.int64)
-        hashes = np.empty(n, dtype=np.uint64) if with_hashes else None
-        self._check(self._fn["encode"](
-            self._h, offsets.ctypes.data, data.ctypes.data, n,
-            ids.ctypes.data, hashes.ctypes.data if with_hashes else None))
-        return (ids, hashes) if with_hashes else ids
-
-    def encode_device(self, d_offsets, d_data, n, d_ids, d_hashes=None):
-        """Device pointers (ints) in, ids (and hashes) written on device;
-        synchronised on return."""
-        self._check(self._fn["encode_device"](
-            self._h, d_offsets, d_data, n, d_ids, d_hashes))
-
-    def decode(self, ids):
-        """int64 ids -> (int32 offsets, uint8 data)."""
-        ids = np.ascontiguousarray(ids, dtype=np.int64)
-        out = AmdStrBatch()
-        self._check(self._fn["decode"](self._h, ids.ctypes.data, len(ids),
-                                       ctypes.byref(out)))
-        _, offsets, data = _strbatch_to_numpy(out)
-        self._fn["free_out"](ctypes.byref(out))
-        return offsets, data
-
-    def drain(self):
-        """Checkpoint: every interned string -> (ids, offsets, data)."""
-        out = AmdStrBatch()
-        self._check(self._fn["checkpoint_drain"](self._h, ctypes.byref(out)))
-        res = _strbatch_to_numpy(out)
-        self._fn["free_out"](ctypes.byref(out))
-        return res
-
-    def restore(self, ids, offsets, data):
-        """Load a drain() into this (empty) handle; every string keeps its
-        id."""
-        ids = np.ascontiguousarray(ids, dtype=np.int64)
-        offsets, data = self._arrow(offsets, data)
-        if len(ids) != len(offsets) - 1:
-            raise ValueError("ids and offsets disagree on the row count")
-        self._check(self._fn["restore"](
-            self._h, ids.ctypes.data, offsets.ctypes.data, data.ctypes.data,
-            len(ids)))
-
-    def count(self):
-        """Number of interned strings."""
-        n = ctypes.c_int64(0)
-        self._check(self._fn["count"](self._h, ctypes.byref(n), None))
-        return int(n.value)
-
-    def profile(self, enable=None):
-        """Switch per-encode timing of the lookup kernel on/off (None leaves
-        it); returns the kernel milliseconds of the last timed encode."""
-        ms = ctypes.c_double(0.0)
-        self._check(self._fn["profile"](
-            self._h, -1 if enable is None else int(bool(enable)),
-            ctypes.byref(ms)))
-        return ms.value
-
-    def arena_used(self):
-        """Arena bytes in use (each string rounded up to 8 bytes)."""
-        used = ctypes.c_int64(0)
-        self._check(self._fn["count"](self._h, None, ctypes.byref(used)))
-        return int(used.value)
-
-    def close(self):
-        if self._h:
-            self._fn["destroy"](self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---- keyed shuffle: stable device partition (arroyo_amd_shuffle_*) --------
@@ -1500,30 +422,677 @@ def make_shuffle_config(n_parts, n_cols, key_col=0, key_mode=AMD_SHUF_KEY_I64,
     return cfg
 
 
-def bind_shuffle(lib, prefix="arroyo_amd_"):
-    """ctypes prototypes of the shuffle family; returns {name: function}."""
-    p = prefix + "shuffle_"
-    vp = ctypes.c_void_p
-    fn = {}
-    fn["create"] = getattr(lib, p + "create")
-    fn["create"].restype = vp
-    fn["create"].argtypes = [ctypes.POINTER(AmdShuffleConfig)]
-    fn["partition_device"] = getattr(lib, p + "partition_device")
-    fn["partition_device"].restype = ctypes.c_int
-    fn["partition_device"].argtypes = [
-        vp, ctypes.POINTER(vp), vp, vp, ctypes.c_int64,
-        ctypes.POINTER(AmdShuffleOut)]
-    fn["bind_output"] = getattr(lib, p + "bind_output")
-    fn["bind_output"].restype = ctypes.c_int
-    fn["bind_output"].argtypes = [vp, ctypes.POINTER(vp), vp, vp]
-    fn["profile"] = getattr(lib, p + "profile")
-    fn["profile"].restype = ctypes.c_int
-    fn["profile"].argtypes = [vp, ctypes.c_int, ctypes.c_int32,
-                              ctypes.POINTER(ctypes.c_double)]
-    fn["destroy"] = getattr(lib, p + "destroy")
-    fn["destroy"].restype = None
-    fn["destroy"].argtypes = [vp]
-    fn["last_error"] = getattr(lib, p + "last_error")
-    fn["last_error"].restype = ctypes.c_char_p
-    fn["last_error"].argtypes = [vp]
+# ---- prototypes: every function of include/arroyo_amd.h, once -------------
+#
+# PROTOTYPES maps the name after the library prefix to (restype, argtypes).
+# A new entry point gets one line here; tests/test_cabi.py holds the table
+# against the header (same names, same parameter counts).
+
+_P = ctypes.POINTER
+_int, _i32, _i64, _u64 = (ctypes.c_int, ctypes.c_int32, ctypes.c_int64,
+                          ctypes.c_uint64)
+_dbl, _vp = ctypes.c_double, ctypes.c_void_p   # _vp: handle or raw address
+_cols, _out, _strs = _P(_vp), _P(AmdOutBatch), _P(AmdStrBatch)
+
+# the recurring shapes (int return unless said otherwise)
+_H = (_vp,)                                    # handle
+_BATCH = (_vp, _cols, _i32, _i64)              # handle, columns, count, rows
+_SIDE_BATCH = (_vp, _i32, _cols, _i32, _i64)   # handle, side, columns, ...
+_NULLABLE = (_vp, _cols, _cols, _i32, _i64)    # columns + validity bitmaps
+_WM_OUT = (_vp, _u64, _out)                    # handle, watermark, out
+_WMS_OUT = (_vp, _P(_u64), _i32, _out)         # handle, watermarks, n, out
+_OUT = (_vp, _out)                             # handle, out
+_SEL_OUT = (_vp, _i32, _out)                   # handle, side / which, out
+_RESTORE_WM = (_int, _u64)                     # has_watermark, watermark
+
+_FAMILIES = {   # symbol infix -> config struct of its create
+    "": AmdWindowConfig, "join_": AmdJoinConfig,
+    "session_": AmdSessionConfig, "expjoin_": AmdExpJoinConfig,
+    "updagg_": AmdUpdatingConfig, "windowfn_": AmdWindowFnConfig,
+    "map_": AmdMapConfig, "strkey_": AmdStrKeyConfig,
+    "shuffle_": AmdShuffleConfig,
+}
+
+_INT_PROTOTYPES = {
+    # sliding / tumbling window aggregate
+    "process_batch": _BATCH,
+    "process_batch_device": _BATCH + (_u64,),
+    "process_batches_device": _BATCH + (_i32, _i32, _u64, _u64),
+    "sync": _H,
+    "handle_watermark": _WM_OUT,
+    "handle_watermarks": _WMS_OUT,
+    "set_filter_watermark": (_vp, _u64),
+    "mark_epoch": _H,
+    "handle_watermarks_epoch": _WMS_OUT,
+    "checkpoint_drain": _OUT,
+    "restore": _BATCH + _RESTORE_WM,
+    "perf": (_vp, _P(_dbl), _P(_i64), _P(_i64), _P(_i64)),
+    "last_emission": _OUT,
+    "partition": (_vp,) * 3 + (_i64, ctypes.c_uint32) + (_vp,) * 3 +
+                 (_P(_u64),),
+    # instant join
+    "join_process_batch": _SIDE_BATCH,
+    "join_process_batch_device": _SIDE_BATCH,
+    "join_handle_watermark": _WM_OUT,
+    "join_checkpoint_drain": _SEL_OUT,
+    # session window aggregate
+    "session_process_batch": _BATCH,
+    "session_process_batch_device": _BATCH + (_u64,),
+    "session_handle_watermark": _WM_OUT,
+    "session_checkpoint_drain": _OUT,
+    "session_drain_values": _OUT,
+    "session_restore_values": _BATCH,
+    "session_restore": _BATCH,
+    # join with expiration
+    "expjoin_process_batch": _SIDE_BATCH + (_out,),
+    "expjoin_process_batch_device": _SIDE_BATCH,
+    "expjoin_collect": _OUT,
+    "expjoin_handle_watermark": (_vp, _u64),
+    "expjoin_match_count": (_vp, _P(_i64)),
+    "expjoin_expire": _H,
+    "expjoin_checkpoint_drain": _SEL_OUT,
+    "expjoin_restore": _SIDE_BATCH + _RESTORE_WM,
+    # updating aggregate
+    "updagg_process_batch": _BATCH,
+    "updagg_process_batch_device": _BATCH,
+    "updagg_process_batch_nullable": _NULLABLE,
+    "updagg_process_batch_nullable_device": _NULLABLE,
+    "updagg_flush": _OUT,
+    "updagg_expire": (_vp, _i64, _out),
+    "updagg_checkpoint_drain": _SEL_OUT,
+    "updagg_restore": _SIDE_BATCH,
+    # ROW_NUMBER window function
+    "windowfn_process_batch": _BATCH,
+    "windowfn_process_batch_device": _BATCH,
+    "windowfn_restore": _BATCH,
+    "windowfn_handle_watermark": _WM_OUT,
+    "windowfn_checkpoint_drain": _OUT,
+    # map / filter / projection
+    "map_process_batch": _BATCH + (_out,),
+    "map_process_batch_device": _BATCH + (_cols, _P(_i64)),
+    # string-key dictionary (buffers go in as raw addresses)
+    "strkey_encode": (_vp, _vp, _vp, _i64, _vp, _vp),
+    "strkey_encode_device": (_vp, _vp, _vp, _i64, _vp, _vp),
+    "strkey_decode": (_vp, _vp, _i64, _strs),
+    "strkey_count": (_vp, _P(_i64), _P(_i64)),
+    "strkey_checkpoint_drain": (_vp, _strs),
+    "strkey_restore": (_vp, _vp, _vp, _vp, _i64),
+    "strkey_profile": (_vp, _int, _P(_dbl)),
+    # keyed shuffle
+    "shuffle_partition_device": (_vp, _cols, _vp, _vp, _i64,
+                                 _P(AmdShuffleOut)),
+    "shuffle_bind_output": (_vp, _cols, _vp, _vp),
+    "shuffle_profile": (_vp, _int, _i32, _P(_dbl)),
+}
+
+PROTOTYPES = {name: (_int, args) for name, args in _INT_PROTOTYPES.items()}
+PROTOTYPES["stream_gbps"] = (_dbl, (_vp, _vp, _i64, _int))
+PROTOTYPES["free_out"] = (None, (_out,))
+PROTOTYPES["strkey_free_out"] = (None, (_strs,))
+for _infix, _cfg in _FAMILIES.items():
+    PROTOTYPES[_infix + "create"] = (_vp, (_P(_cfg),))
+    PROTOTYPES[_infix + "destroy"] = (None, _H)
+    PROTOTYPES[_infix + "last_error"] = (ctypes.c_char_p, _H)
+del _infix, _cfg
+
+
+def declare(lib, prefix):
+    """Give every PROTOTYPES function that `lib` exports its restype and
+    argtypes.  ctypes keeps one function object per name and CDLL, so from
+    here on ``lib.<prefix><name>`` is safe to call from anywhere.  Entries
+    the library lacks are skipped one by one (the oracle has no device,
+    nullable, epoch, strkey or shuffle entry points)."""
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        f = getattr(lib, prefix + name, None)
+        if f is not None:
+            f.restype, f.argtypes = restype, argtypes
+    lib.__dict__["_declared_prefix"] = prefix
+    return lib
+
+
+class _FamilyFns(dict):
+    """{short name: function} of one family; a name the library does not
+    export raises the AttributeError ctypes itself would."""
+
+    def __init__(self, symbol_prefix):
+        super().__init__()
+        self._symbol_prefix = symbol_prefix
+
+    def __missing__(self, name):
+        raise AttributeError(
+            f"undefined symbol: {self._symbol_prefix}{name}")
+
+
+def _family_of(name):
+    """The infix a table name starts with ("" for the window family)."""
+    return next((i for i in _FAMILIES if i and name.startswith(i)), "")
+
+
+def _family_fns(lib, prefix, infix):
+    """The functions of the family `infix` that `lib` exports, by the name
+    after the infix, plus the shared free_out."""
+    if lib.__dict__.get("_declared_prefix") != prefix:
+        declare(lib, prefix)
+    fn = _FamilyFns(prefix + infix)
+    for name in PROTOTYPES:
+        if _family_of(name) == infix and hasattr(lib, prefix + name):
+            fn[name[len(infix):]] = getattr(lib, prefix + name)
+    fn.setdefault("free_out", getattr(lib, prefix + "free_out"))
     return fn
+
+
+def bind(lib, prefix):
+    return _family_fns(lib, prefix, "")
+
+
+def bind_join(lib, prefix):
+    return _family_fns(lib, prefix, "join_")
+
+
+def bind_shuffle(lib, prefix="arroyo_amd_"):
+    """The shuffle family; returns {name: function}."""
+    return _family_fns(lib, prefix, "shuffle_")
+
+
+# ---- batches in and out -----------------------------------------------------
+
+def out_validity(out):
+    """Decode the Arrow validity bitmaps of an AmdOutBatch into per-column
+    numpy bool masks (None = column all-valid)."""
+    n = out.n_rows
+    masks = []
+    if not out.validity:
+        return [None] * out.n_cols
+    for i in range(out.n_cols):
+        bm = out.validity[i]
+        if not bm:
+            masks.append(None)
+            continue
+        nbytes = (n + 7) // 8
+        raw = np.frombuffer(
+            bytes(ctypes.cast(bm, ctypes.POINTER(
+                ctypes.c_uint8 * max(nbytes, 1))).contents),
+            dtype=np.uint8)
+        masks.append(np.unpackbits(raw, bitorder="little")[:n].astype(bool))
+    return masks
+
+
+def pack_validity(mask):
+    """Pack a bool mask into an Arrow validity bitmap (LSB bit order, bit
+    offset 0, (n + 7) // 8 bytes, padding bits clear): the inverse of
+    :func:`out_validity`."""
+    mask = np.ascontiguousarray(mask, dtype=bool)
+    return np.packbits(mask, bitorder="little")
+
+
+def _out_to_numpy(out):
+    """Copy an AmdOutBatch (host memory) into numpy arrays the caller owns;
+    the batch may be freed once this returns."""
+    n = out.n_rows
+    cols = []
+    for i in range(out.n_cols):
+        dt = np.float64 if out.is_f64[i] else np.int64
+        if n == 0:
+            cols.append(np.empty(0, dtype=dt))
+            continue
+        view = (ctypes.c_int64 * n).from_address(out.cols[i])
+        cols.append(np.frombuffer(view, dtype=dt).copy())
+    return cols
+
+
+def _ptr_array(ptrs):
+    """void*[] over raw addresses (ints; None = NULL)."""
+    return (ctypes.c_void_p * len(ptrs))(*ptrs)
+
+
+def _cols_to_ptrs(cols):
+    """Contiguous int64 copies + a void* array over them."""
+    keep = [np.ascontiguousarray(c, dtype=np.int64) for c in cols]
+    return keep, _ptr_array([c.ctypes.data for c in keep])
+
+
+def _batch_args(cols):
+    """The (columns, count, rows) arguments of a host batch, and the arrays
+    they point into (hold these until the call has returned)."""
+    keep, arr = _cols_to_ptrs(cols)
+    return keep, (arr, len(keep), len(keep[0]) if keep else 0)
+
+
+class _Handle:
+    """One operator handle of the family FAMILY (the symbol infix) behind
+    the C ABI: create on construction, destroy on close.  `_h` is the raw
+    handle (None once closed), `_fn` the family's functions by short name,
+    `cfg` the config struct the handle was created from."""
+
+    FAMILY = ""
+    _h = None
+
+    def __init__(self, lib, prefix, cfg):
+        self._fn = _family_fns(lib, prefix, self.FAMILY)
+        self.cfg = cfg
+        self._h = self._fn["create"](ctypes.byref(cfg))
+        if not self._h:
+            raise RuntimeError(
+                f"{prefix}{self.FAMILY}create failed: "
+                f"{self._fn['last_error'](None).decode()}")
+
+    def _check(self, rc):
+        if rc != 0:
+            raise RuntimeError(self._fn["last_error"](self._h).decode())
+
+    def _call(self, name, *args):
+        self._check(self._fn[name](self._h, *args))
+
+    def _call_out(self, name, *args, with_validity=False):
+        """Call a function whose last parameter is an AmdOutBatch*; return
+        its columns as numpy arrays (with with_validity: (cols, masks), a
+        column without a bitmap all True) and free the batch."""
+        out = AmdOutBatch()
+        self._call(name, *args, ctypes.byref(out))
+        cols = _out_to_numpy(out)
+        masks = out_validity(out) if with_validity else None
+        self._fn["free_out"](ctypes.byref(out))
+        if not with_validity:
+            return cols
+        n = len(cols[0]) if cols else 0
+        return cols, [np.ones(n, dtype=bool) if m is None else m
+                      for m in masks]
+
+    def _send(self, name, cols, *lead):
+        """Call a (handle, *lead, columns, count, rows) function on a host
+        batch; returns the arrays that were sent."""
+        keep, batch = _batch_args(cols)
+        self._call(name, *lead, *batch)
+        return keep
+
+    def close(self):
+        if self._h:
+            self._fn["destroy"](self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class WindowOp(_Handle):
+    """One window-aggregate operator instance behind the C ABI.
+
+    Mirrors the ArrowOperator calling convention
+    (crates/arroyo-operator/src/operator.rs:1144-1257): process_batch
+    ingests an owned batch; handle_watermark may emit result batches;
+    single-threaded per handle."""
+
+    def process_batch(self, cols):
+        """cols: list of np.int64 arrays [keys..., values..., _timestamp].
+        Returns the arrays that were sent."""
+        return self._send("process_batch", cols)
+
+    def handle_watermark(self, wm):
+        return self._call_out("handle_watermark", wm)
+
+    def handle_watermarks(self, wms):
+        """Batched watermarks with no rows between them: one device-status
+        round trip serves the whole group.  Semantically identical to
+        handle_watermark in order; returns all emissions concatenated.
+        Falls back to a Python loop where the library lacks the entry
+        point (the oracle)."""
+        if "handle_watermarks" not in self._fn:
+            outs = [self.handle_watermark(w) for w in wms]
+            outs = [o for o in outs if o and len(o[0])]
+            if not outs:
+                return []
+            return [np.concatenate([o[c] for o in outs])
+                    for c in range(len(outs[0]))]
+        return self._call_out("handle_watermarks",
+                              (ctypes.c_uint64 * len(wms))(*wms), len(wms))
+
+    def set_filter_watermark(self, wm):
+        self._call("set_filter_watermark", wm)
+
+    def mark_epoch(self):
+        self._call("mark_epoch")
+
+    def handle_watermarks_epoch(self, wms):
+        return self._call_out("handle_watermarks_epoch",
+                              (ctypes.c_uint64 * len(wms))(*wms), len(wms))
+
+    def checkpoint_drain(self):
+        return self._call_out("checkpoint_drain")
+
+
+class JoinOp(_Handle):
+    """One instant-join operator instance behind the C ABI (left = side 0,
+    right = side 1), mirroring InstantJoin's ArrowOperator surface
+    (crates/arroyo-worker/src/arrow/instant_join.rs)."""
+
+    FAMILY = "join_"
+    LEFT, RIGHT = 0, 1
+
+    def process_batch(self, side, cols):
+        return self._send("process_batch", cols, side)
+
+    def handle_watermark(self, wm):
+        return self._call_out("handle_watermark", wm)
+
+    def checkpoint_drain(self, side):
+        return self._call_out("checkpoint_drain", side)
+
+    def restore(self, side, cols):
+        """on_start re-processes drained batches (instant_join.rs:205-230)."""
+        if cols and len(cols[0]):
+            self.process_batch(side, cols)
+
+
+class SessionOp(_Handle):
+    """One session-window aggregate operator behind the C ABI, mirroring
+    SessionAggregatingWindowFunc's ArrowOperator surface
+    (crates/arroyo-worker/src/arrow/session_aggregating_window.rs)."""
+
+    FAMILY = "session_"
+
+    def process_batch(self, cols):
+        self._send("process_batch", cols)
+
+    def handle_watermark(self, wm):
+        return self._call_out("handle_watermark", wm)
+
+    def checkpoint_drain(self):
+        return self._call_out("checkpoint_drain")
+
+    def restore(self, cols):
+        self._send("restore", cols)
+
+    def drain_values(self):
+        """GPU-only extension (the oracle drains raw rows instead)."""
+        return self._call_out("drain_values")
+
+    def restore_values(self, cols):
+        self._send("restore_values", cols)
+
+
+class ExpJoinOp(_Handle):
+    """One TTL'd (non-windowed) join operator behind the C ABI, mirroring
+    JoinWithExpiration's ArrowOperator surface
+    (crates/arroyo-worker/src/arrow/join_with_expiration.rs)."""
+
+    FAMILY = "expjoin_"
+    LEFT, RIGHT = 0, 1
+
+    def process_batch(self, side, cols):
+        keep, batch = _batch_args(cols)
+        return self._call_out("process_batch", side, *batch)
+
+    def handle_watermark(self, wm):
+        self._call("handle_watermark", wm)
+
+    def process_batch_device(self, side, dptrs, n_rows):
+        """Device-resident ingest (GPU-only extension): dptrs are raw device
+        addresses of the same [key, vals..., ts] columns process_batch
+        takes.  Matches accumulate on the device until collect()."""
+        self._call("process_batch_device", side, _ptr_array(dptrs),
+                   len(dptrs), n_rows)
+
+    def collect(self):
+        """Drain device-accumulated match rows to host numpy columns."""
+        return self._call_out("collect")
+
+    def expire(self):
+        self._call("expire")
+
+    def checkpoint_drain(self, side):
+        return self._call_out("checkpoint_drain", side)
+
+    def restore(self, side, cols, watermark=None):
+        keep, batch = _batch_args(cols)
+        self._call("restore", side, *batch,
+                   1 if watermark is not None else 0,
+                   watermark if watermark is not None else 0)
+
+
+class UpdAggOp(_Handle):
+    """One updating (non-windowed) aggregate operator behind the C ABI,
+    mirroring IncrementalAggregatingFunc's ArrowOperator surface
+    (crates/arroyo-worker/src/arrow/incremental_aggregator.rs)."""
+
+    FAMILY = "updagg_"
+
+    def process_batch(self, cols):
+        self._send("process_batch", cols)
+
+    def process_batch_device(self, dptrs, n_rows):
+        """Device-resident ingest (GPU-only extension): dptrs are raw
+        device addresses of the [keys..., vals..., is_retract] columns."""
+        self._call("process_batch_device", _ptr_array(dptrs), len(dptrs),
+                   n_rows)
+
+    def process_batch_nullable(self, cols, valid):
+        """Nullable ingest (GPU-only extension; the C oracle has no NULLs).
+        cols as for process_batch; valid is None (everything valid) or a
+        list parallel to cols whose entries are None (column all valid) or
+        a bool array (True = non-null)."""
+        keep, (arr, n_cols, n_rows) = _batch_args(cols)
+        varr, vkeep = None, []
+        if valid is not None:
+            if len(valid) != n_cols:
+                raise ValueError(
+                    f"valid has {len(valid)} entries for {n_cols} cols")
+            ptrs = []
+            for m in valid:
+                if m is None:
+                    ptrs.append(None)
+                    continue
+                if len(m) != n_rows:
+                    raise ValueError("validity mask length != n_rows")
+                bm = pack_validity(m)
+                if len(bm) == 0:
+                    bm = np.zeros(1, dtype=np.uint8)
+                vkeep.append(bm)
+                ptrs.append(bm.ctypes.data)
+            varr = _ptr_array(ptrs)
+        self._call("process_batch_nullable", arr, varr, n_cols, n_rows)
+
+    def process_batch_nullable_device(self, dptrs, dvalid_ptrs, n_rows):
+        """Device-resident nullable ingest: dptrs as for
+        process_batch_device; dvalid_ptrs is None or a list parallel to
+        dptrs of None / raw device addresses of Arrow validity bitmaps
+        (8-byte aligned, padded to a multiple of 8 bytes)."""
+        varr = None
+        if dvalid_ptrs is not None:
+            if len(dvalid_ptrs) != len(dptrs):
+                raise ValueError(
+                    f"dvalid_ptrs has {len(dvalid_ptrs)} entries for "
+                    f"{len(dptrs)} cols")
+            varr = _ptr_array(dvalid_ptrs)
+        self._call("process_batch_nullable_device", _ptr_array(dptrs), varr,
+                   len(dptrs), n_rows)
+
+    def flush(self):
+        return self._call_out("flush")
+
+    def flush_with_validity(self):
+        """flush() plus the per-column validity as bool masks (all True for
+        a column without a bitmap): returns (cols, masks)."""
+        return self._call_out("flush", with_validity=True)
+
+    def expire(self, idle_flushes):
+        return self._call_out("expire", idle_flushes)
+
+    def expire_with_validity(self, idle_flushes):
+        return self._call_out("expire", idle_flushes, with_validity=True)
+
+    def checkpoint_drain(self, which):
+        return self._call_out("checkpoint_drain", which)
+
+    def restore(self, which, cols):
+        self._send("restore", cols, which)
+
+
+class WindowFnOp(_Handle):
+    """One ROW_NUMBER window-function operator behind the C ABI, mirroring
+    WindowFunctionOperator's ArrowOperator surface
+    (crates/arroyo-worker/src/arrow/window_fn.rs)."""
+
+    FAMILY = "windowfn_"
+
+    def process_batch(self, cols):
+        self._send("process_batch", cols)
+
+    def process_batch_device(self, dptrs, n_rows):
+        """Device-resident ingest (GPU-only extension): dptrs are raw
+        device addresses of the same columns process_batch takes."""
+        self._call("process_batch_device", _ptr_array(dptrs), len(dptrs),
+                   n_rows)
+
+    def handle_watermark(self, wm):
+        return self._call_out("handle_watermark", wm)
+
+    def checkpoint_drain(self):
+        return self._call_out("checkpoint_drain")
+
+    def restore(self, cols):
+        """Replays the drained rows through process_batch."""
+        if cols and len(cols[0]):
+            self.process_batch(cols)
+
+
+class MapOp(_Handle):
+    """One stateless map/filter/projection operator behind the C ABI,
+    mirroring the expression operators' ArrowOperator surface
+    (crates/arroyo-worker/src/arrow/mod.rs:48-243)."""
+
+    FAMILY = "map_"
+
+    def process_batch_device(self, dptrs, n_rows):
+        """Device-resident map/filter (GPU-only extension): input device
+        addresses in, (device output addresses, surviving row count) out.
+        The returned addresses are owned by the operator and valid until
+        the next process_batch* call."""
+        outp = (ctypes.c_void_p * self.cfg.n_out)()
+        n_out = ctypes.c_int64(0)
+        self._call("process_batch_device", _ptr_array(dptrs), len(dptrs),
+                   n_rows, outp, ctypes.byref(n_out))
+        return [outp[i] for i in range(self.cfg.n_out)], int(n_out.value)
+
+    def process_batch(self, cols):
+        keep, batch = _batch_args(cols)
+        return self._call_out("process_batch", *batch)
+
+
+# ---- Arrow Utf8 helpers and the string-key dictionary ------------------------
+
+def strings_to_arrow(strings):
+    """list[bytes | str] -> (int32 offsets [n + 1], uint8 data): the two
+    buffers of an Arrow Utf8 array.  str items are encoded as UTF-8."""
+    raw = [s.encode("utf-8") if isinstance(s, str) else bytes(s)
+           for s in strings]
+    lens = np.fromiter((len(b) for b in raw), dtype=np.int64, count=len(raw))
+    offsets = np.zeros(len(raw) + 1, dtype=np.int64)
+    np.cumsum(lens, out=offsets[1:])
+    if offsets[-1] > np.iinfo(np.int32).max:
+        raise ValueError("strings exceed the int32 offset range of Utf8")
+    data = np.frombuffer(b"".join(raw), dtype=np.uint8).copy()
+    return offsets.astype(np.int32), data
+
+
+def arrow_to_strings(offsets, data):
+    """(offsets, data) -> list[bytes]; honours a non-zero offsets[0]."""
+    buf = np.ascontiguousarray(data, dtype=np.uint8).tobytes()
+    off = [int(o) for o in offsets]
+    return [buf[off[i]:off[i + 1]] for i in range(len(off) - 1)]
+
+
+def _strbatch_to_numpy(out):
+    n = int(out.n_rows)
+    ids = np.ctypeslib.as_array(out.ids, shape=(n,)).copy() if n else \
+        np.zeros(0, dtype=np.int64)
+    offsets = np.ctypeslib.as_array(out.offsets, shape=(n + 1,)).copy()
+    total = int(offsets[-1])
+    data = np.ctypeslib.as_array(out.data, shape=(total,)).copy() if total \
+        else np.zeros(0, dtype=np.uint8)
+    return ids, offsets, data
+
+
+class StrKeyDict(_Handle):
+    """Device-resident string interner behind the C ABI: Arrow Utf8 key
+    columns in, stable non-negative int64 ids out (and back).  Share one
+    instance between every operator that must agree on the ids."""
+
+    FAMILY = "strkey_"
+
+    @staticmethod
+    def _arrow(offsets, data):
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        if len(offsets) < 1:
+            raise ValueError("offsets needs n_rows + 1 entries")
+        return offsets, data
+
+    def _call_strs(self, name, *args):
+        """Call a function whose last parameter is an AmdStrBatch*; return
+        (ids, offsets, data) and free the batch."""
+        out = AmdStrBatch()
+        self._call(name, *args, ctypes.byref(out))
+        res = _strbatch_to_numpy(out)
+        self._fn["free_out"](ctypes.byref(out))
+        return res
+
+    def encode(self, offsets, data, with_hashes=False):
+        """Host Arrow buffers -> int64 ids (and uint64 content hashes when
+        with_hashes)."""
+        offsets, data = self._arrow(offsets, data)
+        n = len(offsets) - 1
+        ids = np.empty(n, dtype=np.int64)
+        hashes = np.empty(n, dtype=np.uint64) if with_hashes else None
+        self._call("encode", offsets.ctypes.data, data.ctypes.data, n,
+                   ids.ctypes.data,
+                   hashes.ctypes.data if with_hashes else None)
+        return (ids, hashes) if with_hashes else ids
+
+    def encode_device(self, d_offsets, d_data, n, d_ids, d_hashes=None):
+        """Device pointers (ints) in, ids (and hashes) written on device;
+        synchronised on return."""
+        self._call("encode_device", d_offsets, d_data, n, d_ids, d_hashes)
+
+    def decode(self, ids):
+        """int64 ids -> (int32 offsets, uint8 data)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        _, offsets, data = self._call_strs("decode", ids.ctypes.data,
+                                           len(ids))
+        return offsets, data
+
+    def drain(self):
+        """Checkpoint: every interned string -> (ids, offsets, data)."""
+        return self._call_strs("checkpoint_drain")
+
+    def restore(self, ids, offsets, data):
+        """Load a drain() into this (empty) handle; every string keeps its
+        id."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        offsets, data = self._arrow(offsets, data)
+        if len(ids) != len(offsets) - 1:
+            raise ValueError("ids and offsets disagree on the row count")
+        self._call("restore", ids.ctypes.data, offsets.ctypes.data,
+                   data.ctypes.data, len(ids))
+
+    def count(self):
+        """Number of interned strings."""
+        n = ctypes.c_int64(0)
+        self._call("count", ctypes.byref(n), None)
+        return int(n.value)
+
+    def profile(self, enable=None):
+        """Switch per-encode timing of the lookup kernel on/off (None leaves
+        it); returns the kernel milliseconds of the last timed encode."""
+        ms = ctypes.c_double(0.0)
+        self._call("profile", -1 if enable is None else int(bool(enable)),
+                   ctypes.byref(ms))
+        return ms.value
+
+    def arena_used(self):
+        """Arena bytes in use (each string rounded up to 8 bytes)."""
+        used = ctypes.c_int64(0)
+        self._call("count", None, ctypes.byref(used))
+        return int(used.value)

@@ -8,9 +8,8 @@ import ctypes
 import os
 import subprocess
 
-import numpy as np
-
-from arroyo_amd.cabi import AmdOutBatch, WindowOp, _out_to_numpy
+from arroyo_amd.cabi import (WindowOp, _batch_args, _Handle, _ptr_array,
+                             declare)
 
 _DIR = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_DIR, "libarroyo_amd.so")
@@ -45,42 +44,7 @@ def lib():
     if _lib is None:
         if not os.path.exists(_SO):
             build()
-        _lib = ctypes.CDLL(_SO)
-        _lib.arroyo_amd_perf.restype = ctypes.c_int
-        _lib.arroyo_amd_perf.argtypes = [
-            ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
-            ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
-            ctypes.POINTER(ctypes.c_int64)]
-        _lib.arroyo_amd_process_batch_device.restype = ctypes.c_int
-        _lib.arroyo_amd_process_batch_device.argtypes = [
-            ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
-            ctypes.c_int64, ctypes.c_uint64]
-        _lib.arroyo_amd_restore.restype = ctypes.c_int
-        _lib.arroyo_amd_restore.argtypes = [
-            ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
-            ctypes.c_int64, ctypes.c_int, ctypes.c_uint64]
-        _lib.arroyo_amd_process_batches_device.restype = ctypes.c_int
-        _lib.arroyo_amd_process_batches_device.argtypes = [
-            ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
-            ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64,
-            ctypes.c_uint64]
-        _lib.arroyo_amd_stream_gbps.restype = ctypes.c_double
-        _lib.arroyo_amd_stream_gbps.argtypes = [
-            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int]
-        _lib.arroyo_amd_sync.restype = ctypes.c_int
-        _lib.arroyo_amd_sync.argtypes = [ctypes.c_void_p]
-        _lib.arroyo_amd_set_filter_watermark.restype = ctypes.c_int
-        _lib.arroyo_amd_set_filter_watermark.argtypes = [
-            ctypes.c_void_p, ctypes.c_uint64]
-        _lib.arroyo_amd_mark_epoch.restype = ctypes.c_int
-        _lib.arroyo_amd_mark_epoch.argtypes = [ctypes.c_void_p]
-        _lib.arroyo_amd_last_emission.restype = ctypes.c_int
-        _lib.arroyo_amd_last_emission.argtypes = [
-            ctypes.c_void_p, ctypes.POINTER(AmdOutBatch)]
-        _lib.arroyo_amd_partition.restype = ctypes.c_int
-        _lib.arroyo_amd_partition.argtypes = [ctypes.c_void_p] * 3 + [
-            ctypes.c_int64, ctypes.c_uint32] + [ctypes.c_void_p] * 3 + [
-            ctypes.POINTER(ctypes.c_uint64)]
+        _lib = declare(ctypes.CDLL(_SO), "arroyo_amd_")
     return _lib
 
 
@@ -92,55 +56,33 @@ class GpuWindowOp(WindowOp):
 
     def process_batch_device(self, dev_ptrs, n_rows, ts_offset=0):
         """dev_ptrs: list of device pointers (ints) to i64 columns."""
-        arr = (ctypes.c_void_p * len(dev_ptrs))(*dev_ptrs)
-        rc = lib().arroyo_amd_process_batch_device(
-            self._h, arr, len(dev_ptrs), n_rows, ts_offset)
-        if rc != 0:
-            raise RuntimeError(self._fn["last_error"](self._h).decode())
+        self._call("process_batch_device", _ptr_array(dev_ptrs),
+                   len(dev_ptrs), n_rows, ts_offset)
 
     def process_batches_device(self, dev_ptrs, n_rows, reps, contiguous=True,
                                ts_offset0=0, ts_step=0):
-        arr = (ctypes.c_void_p * len(dev_ptrs))(*dev_ptrs)
-        rc = lib().arroyo_amd_process_batches_device(
-            self._h, arr, len(dev_ptrs), n_rows, reps,
-            1 if contiguous else 0, ts_offset0, ts_step)
-        if rc != 0:
-            raise RuntimeError(self._fn["last_error"](self._h).decode())
+        self._call("process_batches_device", _ptr_array(dev_ptrs),
+                   len(dev_ptrs), n_rows, reps, 1 if contiguous else 0,
+                   ts_offset0, ts_step)
 
     def restore(self, cols, watermark=None):
-        cols = [np.ascontiguousarray(c, dtype=np.int64) for c in cols]
-        n_rows = len(cols[0]) if cols else 0
-        arr = (ctypes.c_void_p * len(cols))(
-            *[c.ctypes.data_as(ctypes.c_void_p).value for c in cols])
-        rc = lib().arroyo_amd_restore(
-            self._h, arr, len(cols), n_rows,
-            1 if watermark is not None else 0,
-            watermark if watermark is not None else 0)
-        if rc != 0:
-            raise RuntimeError(self._fn["last_error"](self._h).decode())
+        keep, batch = _batch_args(cols)
+        self._call("restore", *batch, 1 if watermark is not None else 0,
+                   watermark if watermark is not None else 0)
 
     def last_emission(self):
         """Host copy of the window emissions still resident in the device
         output buffers (the latest fired window per fire stream), as numpy
         columns [key?, aggs..., window_start, window_end, _timestamp]."""
-        out = AmdOutBatch()
-        rc = lib().arroyo_amd_last_emission(self._h, ctypes.byref(out))
-        if rc != 0:
-            raise RuntimeError(self._fn["last_error"](self._h).decode())
-        cols = _out_to_numpy(out)
-        self._fn["free_out"](ctypes.byref(out))
-        return cols
+        return self._call_out("last_emission")
 
     def perf(self):
         ms = ctypes.c_double()
         rows = ctypes.c_int64()
         launches = ctypes.c_int64()
         emitted = ctypes.c_int64()
-        rc = lib().arroyo_amd_perf(self._h, ctypes.byref(ms),
-                                   ctypes.byref(rows), ctypes.byref(launches),
-                                   ctypes.byref(emitted))
-        if rc != 0:
-            raise RuntimeError(self._fn["last_error"](self._h).decode())
+        self._call("perf", ctypes.byref(ms), ctypes.byref(rows),
+                   ctypes.byref(launches), ctypes.byref(emitted))
         return {"update_ms": ms.value, "rows": rows.value,
                 "launches": launches.value,
                 "emitted_device_rows": emitted.value}
@@ -196,7 +138,7 @@ def make_strkey(cfg):
     return StrKeyDict(lib(), "arroyo_amd_", cfg)
 
 
-class Shuffler:
+class Shuffler(_Handle):
     """Stable device partition for the keyed shuffle (arroyo_amd_shuffle_*):
     up to 16 8-byte columns and optionally one Arrow Utf8 column, split
     into n_parts contiguous segments, rows of a segment in input order.
@@ -207,14 +149,10 @@ class Shuffler:
     only partition_ptrs() is available and the results stay in the handle's
     own buffers, for chaining into another handle's *_device call."""
 
+    FAMILY = "shuffle_"
+
     def __init__(self, cfg, bind_output=True):
-        from arroyo_amd.cabi import bind_shuffle
-        self._fn = bind_shuffle(lib())
-        self.cfg = cfg
-        self._h = self._fn["create"](ctypes.byref(cfg))
-        if not self._h:
-            raise RuntimeError("arroyo_amd_shuffle_create failed: " +
-                               self._fn["last_error"](None).decode())
+        super().__init__(lib(), "arroyo_amd_", cfg)
         self._out = None
         if bind_output:
             import torch
@@ -227,24 +165,19 @@ class Shuffler:
                                   dtype=torch.int32, device=dev)
                 data = torch.empty(max(cfg.max_bytes, 1), dtype=torch.uint8,
                                    device=dev)
-            arr = (ctypes.c_void_p * cfg.n_cols)(*[c.data_ptr() for c in cols])
-            self._check(self._fn["bind_output"](
-                self._h, arr, off.data_ptr() if cfg.has_utf8 else None,
-                data.data_ptr() if cfg.has_utf8 else None))
+            self._call("bind_output",
+                       _ptr_array([c.data_ptr() for c in cols]),
+                       off.data_ptr() if cfg.has_utf8 else None,
+                       data.data_ptr() if cfg.has_utf8 else None)
             self._out = (cols, off, data)
-
-    def _check(self, rc):
-        if rc != 0:
-            raise RuntimeError(self._fn["last_error"](self._h).decode())
 
     def partition_ptrs(self, dev_ptrs, n_rows, d_offsets=None, d_data=None):
         """Device addresses (ints, None = NULL) in, AmdShuffleOut out; its
         device pointers are valid until the next call on this handle."""
         from arroyo_amd.cabi import AmdShuffleOut
-        arr = (ctypes.c_void_p * len(dev_ptrs))(*dev_ptrs)
         out = AmdShuffleOut()
-        self._check(self._fn["partition_device"](
-            self._h, arr, d_offsets, d_data, n_rows, ctypes.byref(out)))
+        self._call("partition_device", _ptr_array(dev_ptrs), d_offsets,
+                   d_data, n_rows, ctypes.byref(out))
         return out
 
     def partition(self, cols, utf8=None):
@@ -292,22 +225,13 @@ class Shuffler:
         milliseconds of the last timed call by kernel name."""
         from arroyo_amd.cabi import AMD_SHUF_N_KERNELS, SHUF_KERNEL_NAMES
         ms = (ctypes.c_double * AMD_SHUF_N_KERNELS)()
-        self._check(self._fn["profile"](
-            self._h, -1 if enable is None else int(bool(enable)),
-            -1 if copy_threshold is None else int(copy_threshold), ms))
+        self._call("profile", -1 if enable is None else int(bool(enable)),
+                   -1 if copy_threshold is None else int(copy_threshold), ms)
         return dict(zip(SHUF_KERNEL_NAMES, ms))
 
     def close(self):
-        if self._h:
-            self._fn["destroy"](self._h)
-            self._h = None
-            self._out = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
+        self._out = None
 
 
 def make_shuffler(cfg, bind_output=True):

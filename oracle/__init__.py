@@ -25,7 +25,8 @@ def build(force=False):
 def lib():
     global _lib
     if _lib is None:
-        _lib = ctypes.CDLL(build())
+        from arroyo_amd.cabi import declare
+        _lib = declare(ctypes.CDLL(build()), "oracle_")
     return _lib
 
 

@@ -84,14 +84,10 @@ def bench_expjoin_device():
         ts = T0 + np.full(n, i, dtype=np.int64) * NS
         tens.append([torch.from_numpy(c).to(dev) for c in (k, v, ts)])
     import ctypes
-    lib = gpu.lib()
-    lib.arroyo_amd_expjoin_match_count.restype = ctypes.c_int
-    lib.arroyo_amd_expjoin_match_count.argtypes = [
-        ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]
 
     def consume():
         c = ctypes.c_int64()
-        rc = lib.arroyo_amd_expjoin_match_count(op._h, ctypes.byref(c))
+        rc = op._fn["match_count"](op._h, ctypes.byref(c))
         if rc != 0:
             raise RuntimeError(op._fn["last_error"](op._h).decode())
         return int(c.value)

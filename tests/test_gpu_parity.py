@@ -232,8 +232,6 @@ def test_table_full_fails_loudly():
 def test_partition_kernel_matches_host():
     """K8: device partition ids must match the host restatement of
     server_for_hash (splitmix64 over contiguous u64 ranges)."""
-    import ctypes
-
     from arroyo_amd import gpu
 
     def splitmix64(x):
@@ -248,8 +246,6 @@ def test_partition_kernel_matches_host():
     vals = rng.integers(0, 100, size=n).astype(np.int64)
     ts = np.arange(n, dtype=np.int64)
 
-    lib = gpu.lib()
-    lib.arroyo_amd_create.restype = ctypes.c_void_p  # ensure loaded
     import torch
     dk = torch.from_numpy(keys).cuda()
     dv = torch.from_numpy(vals).cuda()

@@ -61,11 +61,6 @@ def test_strkey_create_without_gpu_fails_loudly():
     from arroyo_amd import gpu
     lib = gpu.lib()
     cfg = cabi.make_strkey_config()
-    lib.arroyo_amd_strkey_create.restype = ctypes.c_void_p
-    lib.arroyo_amd_strkey_create.argtypes = [
-        ctypes.POINTER(cabi.AmdStrKeyConfig)]
-    lib.arroyo_amd_strkey_last_error.restype = ctypes.c_char_p
-    lib.arroyo_amd_strkey_last_error.argtypes = [ctypes.c_void_p]
     h = lib.arroyo_amd_strkey_create(ctypes.byref(cfg))
     assert not h, "create must fail without a HIP device (no CPU fallback)"
     msg = lib.arroyo_amd_strkey_last_error(None).decode()
