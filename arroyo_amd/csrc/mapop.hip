@@ -13,15 +13,20 @@
  * ordered scatter, three launches per batch on one stream.
  *
  * Parity is pinned against oracle/arroyo_oracle.c by tests/test_mapop.py
- * (bit-exact, including the f64 bit patterns).
+ * (bit-exact, including the f64 bit patterns); every opcode's semantics,
+ * the launch shapes and the device surface are pinned against an
+ * independent reference by tests/test_mapop_ops.py.
  */
 #include <hipcub/hipcub.hpp>
 
 #include "op_common.h"
+#include "../../include/arroyo_amd_map_check.h"
 
 namespace mapop {
 
-#define MERR_DIV0 1
+#define MERR_DIV0     1
+#define MERR_OVERFLOW 2       /* INT64_MIN / -1 */
+#define MERR_CAST     3       /* F2I of NaN, +-inf or outside [-2^63, 2^63) */
 
 struct MapArgs {
     const int64_t *cols[AMD_MAP_MAX_REGS];
@@ -33,24 +38,35 @@ struct MapArgs {
     int *err;
 };
 
+/* Row arithmetic, restated from arrow-arith / DataFusion (COVERAGE.md row
+ * 3): + - * wrap (unsigned arithmetic: no signed-overflow UB); DIV
+ * truncates, errors on b == 0 and on INT64_MIN / -1; MOD takes the
+ * dividend's sign, errors on b == 0, and x % -1 == 0 for every x; compares
+ * and AND/OR/NOT see the raw i64 and give exactly 0 or 1; F2I truncates and
+ * errors on NaN, +-inf and anything outside [-2^63, 2^63); f64 ops are IEEE
+ * binary64.  A row error stops that row's program; the call then fails and
+ * the row's outputs are never read.  Rows that raise different errors race
+ * on the error word: which one is reported is unspecified. */
 __device__ inline void map_eval(const AmdMapConfig &c, int64_t *regs,
                                 int *err) {
     for (int i = 0; i < c.n_prog; i++) {
         const AmdMapInstr &in = c.prog[i];
         int64_t a = regs[in.a], b = regs[in.b], v = 0;
+        uint64_t ua = (uint64_t)a, ub = (uint64_t)b;
         double fa = __longlong_as_double(a), fb = __longlong_as_double(b);
         switch (in.op) {
         case AMD_MOP_CONST: v = in.imm; break;
-        case AMD_MOP_ADD: v = a + b; break;
-        case AMD_MOP_SUB: v = a - b; break;
-        case AMD_MOP_MUL: v = a * b; break;
+        case AMD_MOP_ADD: v = (int64_t)(ua + ub); break;
+        case AMD_MOP_SUB: v = (int64_t)(ua - ub); break;
+        case AMD_MOP_MUL: v = (int64_t)(ua * ub); break;
         case AMD_MOP_DIV:
             if (b == 0) { *err = MERR_DIV0; return; }
+            if (a == INT64_MIN && b == -1) { *err = MERR_OVERFLOW; return; }
             v = a / b;
             break;
         case AMD_MOP_MOD:
             if (b == 0) { *err = MERR_DIV0; return; }
-            v = a % b;
+            v = b == -1 ? 0 : a % b;
             break;
         case AMD_MOP_EQ: v = a == b; break;
         case AMD_MOP_NE: v = a != b; break;
@@ -62,7 +78,11 @@ __device__ inline void map_eval(const AmdMapConfig &c, int64_t *regs,
         case AMD_MOP_OR: v = (a != 0) || (b != 0); break;
         case AMD_MOP_NOT: v = a == 0; break;
         case AMD_MOP_I2F: v = __double_as_longlong((double)a); break;
-        case AMD_MOP_F2I: v = (int64_t)fa; break;
+        case AMD_MOP_F2I:
+            /* 0x1p63 == 2^63; a NaN fails both compares */
+            if (!(fa >= -0x1p63 && fa < 0x1p63)) { *err = MERR_CAST; return; }
+            v = (int64_t)fa;
+            break;
         case AMD_MOP_FADD: v = __double_as_longlong(fa + fb); break;
         case AMD_MOP_FSUB: v = __double_as_longlong(fa - fb); break;
         case AMD_MOP_FMUL: v = __double_as_longlong(fa * fb); break;
@@ -123,21 +143,14 @@ struct GpuMap : OpBase {
 };
 
 API void *arroyo_amd_map_create(const AmdMapConfig *cfg) {
-    if (!cfg || cfg->n_in_cols < 1 || cfg->n_in_cols > AMD_MAP_MAX_REGS ||
-        cfg->n_prog < 0 || cfg->n_prog > AMD_MAP_MAX_PROG ||
-        cfg->n_out < 1 || cfg->n_out > 6 ||
-        cfg->filter_reg >= AMD_MAP_MAX_REGS) {
-        snprintf(g_create_err, sizeof g_create_err,
-                 "invalid map config (n_out <= 6 on the GPU path)");
+    /* k_map_scatter takes its columns as six kernel arguments */
+    const char *bad = amd_map_config_error(cfg, AMD_MAP_MAX_OUT);
+    if (!bad && cfg->n_out > 6)
+        bad = "invalid map config: n_out <= 6 on the GPU path";
+    if (bad) {
+        snprintf(g_create_err, sizeof g_create_err, "%s", bad);
         return nullptr;
     }
-    for (int i = 0; i < cfg->n_prog; i++)
-        if (cfg->prog[i].dst < 0 || cfg->prog[i].dst >= AMD_MAP_MAX_REGS ||
-            cfg->prog[i].a < 0 || cfg->prog[i].a >= AMD_MAP_MAX_REGS ||
-            cfg->prog[i].b < 0 || cfg->prog[i].b >= AMD_MAP_MAX_REGS) {
-            snprintf(g_create_err, sizeof g_create_err, "invalid map program");
-            return nullptr;
-        }
     GpuMap *o = new GpuMap();
     o->cfg = *cfg;
     o->cap = 1 << 20;
@@ -170,7 +183,14 @@ API const char *arroyo_amd_map_last_error(void *h) {
     return h ? ((GpuMap *)h)->err_msg : g_create_err;
 }
 
-static const char *map_err_msg(int) { return "division by zero"; }
+static const char *map_err_msg(int e) {
+    switch (e) {
+    case MERR_DIV0: return "division by zero";
+    case MERR_OVERFLOW: return "integer overflow in division";
+    case MERR_CAST: return "cast of f64 to i64 out of range";
+    }
+    return "unknown map error";
+}
 
 /* evaluate the program over n_rows device rows, compact by the filter and
  * read the error word.  src[i] = where output column i landed, *n_keep =
@@ -220,7 +240,12 @@ static int map_eval(GpuMap *o, const int64_t *const *dcols, int32_t n_cols,
     }
     if (c.filter_reg >= 0)
         for (int i = 0; i < c.n_out; i++) src[i] = o->d_out[i];
-    return op_check_err(o, map_err_msg);
+    if (!op_check_err(o, map_err_msg)) return 0;
+    /* reported once: clear the word so the next batch is judged afresh
+     * (err_msg already holds this batch's message) */
+    if (hipMemsetAsync(o->d_err, 0, 4, o->stream) == hipSuccess)
+        (void)hipStreamSynchronize(o->stream);
+    return 1;
 }
 
 static int map_check_cols(GpuMap *o, int32_t n_cols) {

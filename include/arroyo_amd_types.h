@@ -307,9 +307,33 @@ typedef struct {
  * `out_reg` names the emitted columns (KeyExecutionOperator = key exprs
  * first), and `filter_reg` (when >= 0) keeps rows whose register is
  * nonzero, preserving row order like the reference's filter kernels.
- * Integer division/modulo by zero is a loud error (DataFusion errors too);
- * f64 ops follow IEEE.  i64 values and f64 bit patterns share the
- * register file; AMD_MOP_I2F / F2I convert. */
+ * i64 values and f64 bit patterns share the register file; AMD_MOP_I2F /
+ * F2I convert.
+ *
+ * Arithmetic (restated from arrow-arith / DataFusion, pinned by
+ * tests/test_mapop_ops.py):
+ *   ADD SUB MUL   two's-complement wrapping
+ *   DIV           truncates toward zero; b == 0 -> error "division by
+ *                 zero"; INT64_MIN / -1 -> error "integer overflow ..."
+ *   MOD           sign of the dividend; b == 0 -> "division by zero";
+ *                 x % -1 == 0 for every x, INT64_MIN included
+ *   EQ .. GE      signed 64-bit compare of the raw register (there are no
+ *                 float compares); result exactly 0 or 1
+ *   AND OR NOT    truthiness is != 0; result exactly 0 or 1
+ *   I2F           round to nearest even
+ *   F2I           truncates toward zero; NaN, +-inf or a value outside
+ *                 [-2^63, 2^63) -> error "cast ... out of range"
+ *   FADD .. FDIV  IEEE binary64, correctly rounded, subnormals kept
+ *   filter        keeps a row iff the register is non-zero as an integer
+ *                 (so the bit pattern of -0.0 is kept)
+ * After a row error the call fails and returns no output; the next batch on
+ * the handle is evaluated afresh.  If rows of one batch raise different
+ * errors, which one is reported is unspecified.
+ *
+ * A config is validated at create (include/arroyo_amd_map_check.h): opcodes
+ * and registers in range, and every register that is read -- by an
+ * instruction, out_reg[] or filter_reg -- is an input register or the dst
+ * of an earlier instruction. */
 enum AmdMapOp {
     AMD_MOP_CONST = 0,  /* dst = imm */
     AMD_MOP_ADD, AMD_MOP_SUB, AMD_MOP_MUL, AMD_MOP_DIV, AMD_MOP_MOD,

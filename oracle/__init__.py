@@ -8,13 +8,15 @@ import subprocess
 _DIR = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_DIR, "liboracle.so")
 _SRC = os.path.join(_DIR, "arroyo_oracle.c")
+_HDR = os.path.join(_DIR, "..", "include", "arroyo_amd_map_check.h")
 
 _lib = None
 
 
 def build(force=False):
     if force or not os.path.exists(_SO) or \
-            os.path.getmtime(_SO) < os.path.getmtime(_SRC):
+            os.path.getmtime(_SO) < max(os.path.getmtime(_SRC),
+                                        os.path.getmtime(_HDR)):
         subprocess.run(
             ["gcc", "-O2", "-g", "-shared", "-fPIC", "-fvisibility=hidden",
              "-o", _SO, _SRC, "-lm"],

@@ -37,6 +37,7 @@
 #include <stdio.h>
 
 #include "../include/arroyo_amd_types.h"
+#include "../include/arroyo_amd_map_check.h"
 
 #define ORACLE_API __attribute__((visibility("default")))
 
@@ -2445,40 +2446,52 @@ typedef struct {
     char err[256];
 } MOp;
 
+/* why the last oracle_map_create returned NULL */
+static const char *map_create_err = "null handle / invalid config";
+
 ORACLE_API void *oracle_map_create(const AmdMapConfig *cfg) {
-    if (!cfg || cfg->n_in_cols < 1 || cfg->n_in_cols > AMD_MAP_MAX_REGS ||
-        cfg->n_prog < 0 || cfg->n_prog > AMD_MAP_MAX_PROG ||
-        cfg->n_out < 1 || cfg->n_out > AMD_MAP_MAX_OUT)
+    const char *bad = amd_map_config_error(cfg, AMD_MAP_MAX_OUT);
+    if (bad) {
+        map_create_err = bad;
         return NULL;
-    for (int i = 0; i < cfg->n_prog; i++)
-        if (cfg->prog[i].dst < 0 || cfg->prog[i].dst >= AMD_MAP_MAX_REGS ||
-            cfg->prog[i].a < 0 || cfg->prog[i].a >= AMD_MAP_MAX_REGS ||
-            cfg->prog[i].b < 0 || cfg->prog[i].b >= AMD_MAP_MAX_REGS)
-            return NULL;
+    }
     MOp *o = calloc(1, sizeof(MOp));
     o->cfg = *cfg;
     return o;
 }
 
 ORACLE_API const char *oracle_map_last_error(void *h) {
-    return h ? ((MOp *)h)->err : "null handle / invalid config";
+    return h ? ((MOp *)h)->err : map_create_err;
 }
 
+/* Row arithmetic, restated from arrow-arith / DataFusion (COVERAGE.md row
+ * 3): + - * wrap (unsigned arithmetic: no signed-overflow UB); DIV
+ * truncates, errors on b == 0 and on INT64_MIN / -1; MOD takes the
+ * dividend's sign, errors on b == 0, and x % -1 == 0 for every x; compares
+ * and AND/OR/NOT see the raw i64 and give exactly 0 or 1; F2I truncates and
+ * errors on NaN, +-inf and anything outside [-2^63, 2^63); f64 ops are IEEE
+ * binary64.  A batch whose rows raise different errors reports one of them,
+ * which one is unspecified. */
 static int map_eval_row(const AmdMapConfig *c, const int64_t *const *cols,
                         int64_t r, int64_t *regs, char *err) {
     for (int i = 0; i < c->n_in_cols; i++) regs[i] = cols[i][r];
     for (int i = 0; i < c->n_prog; i++) {
         const AmdMapInstr *in = &c->prog[i];
         int64_t a = regs[in->a], b = regs[in->b], v = 0;
+        uint64_t ua = (uint64_t)a, ub = (uint64_t)b;
         double fa = bits_to_d(a), fb = bits_to_d(b);
         switch (in->op) {
         case AMD_MOP_CONST: v = in->imm; break;
-        case AMD_MOP_ADD: v = a + b; break;
-        case AMD_MOP_SUB: v = a - b; break;
-        case AMD_MOP_MUL: v = a * b; break;
+        case AMD_MOP_ADD: v = (int64_t)(ua + ub); break;
+        case AMD_MOP_SUB: v = (int64_t)(ua - ub); break;
+        case AMD_MOP_MUL: v = (int64_t)(ua * ub); break;
         case AMD_MOP_DIV:
             if (b == 0) {
                 snprintf(err, 256, "division by zero");
+                return 1;
+            }
+            if (a == INT64_MIN && b == -1) {
+                snprintf(err, 256, "integer overflow in division");
                 return 1;
             }
             v = a / b;
@@ -2488,7 +2501,7 @@ static int map_eval_row(const AmdMapConfig *c, const int64_t *const *cols,
                 snprintf(err, 256, "division by zero");
                 return 1;
             }
-            v = a % b;
+            v = b == -1 ? 0 : a % b;
             break;
         case AMD_MOP_EQ: v = a == b; break;
         case AMD_MOP_NE: v = a != b; break;
@@ -2500,7 +2513,14 @@ static int map_eval_row(const AmdMapConfig *c, const int64_t *const *cols,
         case AMD_MOP_OR: v = (a != 0) || (b != 0); break;
         case AMD_MOP_NOT: v = a == 0; break;
         case AMD_MOP_I2F: v = d_to_bits((double)a); break;
-        case AMD_MOP_F2I: v = (int64_t)fa; break;
+        case AMD_MOP_F2I:
+            /* 0x1p63 == 2^63; a NaN fails both compares */
+            if (!(fa >= -0x1p63 && fa < 0x1p63)) {
+                snprintf(err, 256, "cast of f64 to i64 out of range");
+                return 1;
+            }
+            v = (int64_t)fa;
+            break;
         case AMD_MOP_FADD: v = d_to_bits(fa + fb); break;
         case AMD_MOP_FSUB: v = d_to_bits(fa - fb); break;
         case AMD_MOP_FMUL: v = d_to_bits(fa * fb); break;
@@ -2530,9 +2550,14 @@ ORACLE_API int oracle_map_process_batch(void *h, const int64_t *const *cols,
         out->is_f64[i] = c->out_is_f64[i];
     }
     int64_t w = 0;
-    int64_t regs[AMD_MAP_MAX_REGS] = {0};
     for (int64_t r = 0; r < n_rows; r++) {
-        if (map_eval_row(c, cols, r, regs, o->err)) return 1;
+        /* per row, like the kernel's: nothing carries over between rows */
+        int64_t regs[AMD_MAP_MAX_REGS] = {0};
+        if (map_eval_row(c, cols, r, regs, o->err)) {
+            /* a row error returns no output */
+            oracle_free_out(out);
+            return 1;
+        }
         if (c->filter_reg >= 0 && regs[c->filter_reg] == 0) continue;
         for (int i = 0; i < c->n_out; i++)
             ((int64_t *)out->cols[i])[w] = regs[c->out_reg[i]];
