@@ -291,6 +291,9 @@ MOP_CONST, MOP_ADD, MOP_SUB, MOP_MUL, MOP_DIV, MOP_MOD = range(6)
 MOP_EQ, MOP_NE, MOP_LT, MOP_LE, MOP_GT, MOP_GE = range(6, 12)
 MOP_AND, MOP_OR, MOP_NOT, MOP_I2F, MOP_F2I = range(12, 17)
 MOP_FADD, MOP_FSUB, MOP_FMUL, MOP_FDIV = range(17, 21)
+# null_semantics=1 programs only; SELECT's else-register goes in imm
+MOP_IS_NULL, MOP_IS_NOT_NULL, MOP_COALESCE, MOP_NULLIF, MOP_SELECT = \
+    range(21, 26)
 
 
 class AmdMapInstr(ctypes.Structure):
@@ -310,13 +313,17 @@ class AmdMapConfig(ctypes.Structure):
         ("filter_reg", ctypes.c_int32),
         ("device", ctypes.c_int32),
         ("emit_to_host", ctypes.c_int32),
+        ("null_semantics", ctypes.c_int32),
     ]
 
 
 def make_map_config(n_in_cols, prog, out_reg, out_is_f64=None,
-                    filter_reg=-1, device=0):
+                    filter_reg=-1, device=0, null_semantics=0):
     """prog: list of (op, a, b, dst[, imm]) tuples.  imm may be a float for
-    MOP_CONST feeding f64 ops (stored as the f64 bit pattern)."""
+    MOP_CONST feeding f64 ops (stored as the f64 bit pattern); for
+    MOP_SELECT it is the else-branch register.  null_semantics=1: SQL NULL
+    semantics (validity per register, opcodes 21..25; see AmdMapConfig in
+    arroyo_amd_types.h)."""
     import struct
     cfg = AmdMapConfig()
     cfg.n_in_cols = n_in_cols
@@ -338,6 +345,7 @@ def make_map_config(n_in_cols, prog, out_reg, out_is_f64=None,
     cfg.filter_reg = filter_reg
     cfg.device = device
     cfg.emit_to_host = 1
+    cfg.null_semantics = int(null_semantics)
     return cfg
 
 
@@ -510,6 +518,9 @@ _INT_PROTOTYPES = {
     # map / filter / projection
     "map_process_batch": _BATCH + (_out,),
     "map_process_batch_device": _BATCH + (_cols, _P(_i64)),
+    "map_process_batch_nullable": _NULLABLE + (_out,),
+    "map_process_batch_nullable_device":
+        _NULLABLE + (_cols, _cols, _P(_i64), _P(_i64)),
     # string-key dictionary (buffers go in as raw addresses)
     "strkey_encode": (_vp, _vp, _vp, _i64, _vp, _vp),
     "strkey_encode_device": (_vp, _vp, _vp, _i64, _vp, _vp),
@@ -656,6 +667,30 @@ def _batch_args(cols):
     they point into (hold these until the call has returned)."""
     keep, arr = _cols_to_ptrs(cols)
     return keep, (arr, len(keep), len(keep[0]) if keep else 0)
+
+
+def _validity_args(valid, n_cols, n_rows):
+    """The validity argument of a nullable host batch: `valid` is None
+    (everything valid) or a list parallel to the columns of None (column
+    all valid) / bool arrays (True = non-null).  Returns the packed bitmaps
+    (hold these until the call has returned) and the pointer array."""
+    if valid is None:
+        return [], None
+    if len(valid) != n_cols:
+        raise ValueError(f"valid has {len(valid)} entries for {n_cols} cols")
+    keep, ptrs = [], []
+    for m in valid:
+        if m is None:
+            ptrs.append(None)
+            continue
+        if len(m) != n_rows:
+            raise ValueError("validity mask length != n_rows")
+        bm = pack_validity(m)
+        if len(bm) == 0:
+            bm = np.zeros(1, dtype=np.uint8)
+        keep.append(bm)
+        ptrs.append(bm.ctypes.data)
+    return keep, _ptr_array(ptrs)
 
 
 class _Handle:
@@ -874,24 +909,7 @@ class UpdAggOp(_Handle):
         list parallel to cols whose entries are None (column all valid) or
         a bool array (True = non-null)."""
         keep, (arr, n_cols, n_rows) = _batch_args(cols)
-        varr, vkeep = None, []
-        if valid is not None:
-            if len(valid) != n_cols:
-                raise ValueError(
-                    f"valid has {len(valid)} entries for {n_cols} cols")
-            ptrs = []
-            for m in valid:
-                if m is None:
-                    ptrs.append(None)
-                    continue
-                if len(m) != n_rows:
-                    raise ValueError("validity mask length != n_rows")
-                bm = pack_validity(m)
-                if len(bm) == 0:
-                    bm = np.zeros(1, dtype=np.uint8)
-                vkeep.append(bm)
-                ptrs.append(bm.ctypes.data)
-            varr = _ptr_array(ptrs)
+        vkeep, varr = _validity_args(valid, n_cols, n_rows)
         self._call("process_batch_nullable", arr, varr, n_cols, n_rows)
 
     def process_batch_nullable_device(self, dptrs, dvalid_ptrs, n_rows):
@@ -979,6 +997,51 @@ class MapOp(_Handle):
     def process_batch(self, cols):
         keep, batch = _batch_args(cols)
         return self._call_out("process_batch", *batch)
+
+    def process_batch_nullable(self, cols, valid):
+        """SQL NULLs in and out (GPU-only extension, null_semantics=1
+        handles).  cols as for process_batch; valid is None (everything
+        valid) or a list parallel to cols whose entries are None (column all
+        valid) or a bool array (True = non-null).  Returns (cols, masks):
+        masks[i] is output column i's validity as a bool array, all True
+        for a column that came back without a bitmap; the value under a
+        NULL is 0."""
+        keep, (arr, n_cols, n_rows) = _batch_args(cols)
+        vkeep, varr = _validity_args(valid, n_cols, n_rows)
+        return self._call_out("process_batch_nullable", arr, varr, n_cols,
+                              n_rows, with_validity=True)
+
+    def process_batch_with_validity(self, cols):
+        """process_batch on a null_semantics=1 handle: every input valid,
+        (cols, masks) out as from process_batch_nullable."""
+        keep, batch = _batch_args(cols)
+        return self._call_out("process_batch", *batch, with_validity=True)
+
+    def process_batch_nullable_device(self, dptrs, dvalid_ptrs, n_rows):
+        """Device-resident counterpart: dptrs as for process_batch_device;
+        dvalid_ptrs is None or a list parallel to dptrs of None / raw device
+        addresses of Arrow validity bitmaps (8-byte aligned, padded to a
+        multiple of 8 bytes).  Returns (output column addresses, output
+        bitmap addresses, NULL count per output column, surviving rows);
+        the addresses are owned by the operator and valid until the next
+        process_batch* call, the bitmaps 8-byte aligned and padded to 8
+        bytes with the padding bits clear."""
+        varr = None
+        if dvalid_ptrs is not None:
+            if len(dvalid_ptrs) != len(dptrs):
+                raise ValueError(
+                    f"dvalid_ptrs has {len(dvalid_ptrs)} entries for "
+                    f"{len(dptrs)} cols")
+            varr = _ptr_array(dvalid_ptrs)
+        n = self.cfg.n_out
+        outp, outv = (ctypes.c_void_p * n)(), (ctypes.c_void_p * n)()
+        nulls = (ctypes.c_int64 * n)()
+        n_out = ctypes.c_int64(0)
+        self._call("process_batch_nullable_device", _ptr_array(dptrs), varr,
+                   len(dptrs), n_rows, outp, outv, nulls,
+                   ctypes.byref(n_out))
+        return ([outp[i] for i in range(n)], [outv[i] for i in range(n)],
+                [int(nulls[i]) for i in range(n)], int(n_out.value))
 
 
 # ---- Arrow Utf8 helpers and the string-key dictionary ------------------------

@@ -53,3 +53,28 @@ inline uint8_t *out_validity_col(AmdOutBatch *out, int c) {
     free(out->validity[c]);
     return out->validity[c] = (uint8_t *)calloc(nbytes ? nbytes : 1, 1);
 }
+
+/* Append the first n_bits bits of the Arrow bitmap `src` (bit offset 0; its
+ * bits past n_bits may hold anything) to `dst` at bit offset dst_bit;
+ * src == nullptr appends n_bits ones.  `dst` is a bitmap filled front to
+ * back: its bits from dst_bit on are clear on entry, and those from
+ * dst_bit + n_bits on are still clear on return.  It must hold
+ * (dst_bit + n_bits + 7) / 8 bytes; no byte past that is touched.  This is
+ * how a filtered operator joins the bitmaps of its chunks, whose kept counts
+ * are no multiple of 8. */
+inline void out_validity_append_bits(uint8_t *dst, int64_t dst_bit,
+                                     const uint8_t *src, int64_t n_bits) {
+    if (n_bits <= 0) return;
+    unsigned sh = (unsigned)(dst_bit & 7);
+    uint8_t *d = dst + (dst_bit >> 3);
+    int64_t n_bytes = (n_bits + 7) >> 3;
+    unsigned tail = (unsigned)(n_bits & 7);
+    for (int64_t i = 0; i < n_bytes; i++) {
+        unsigned b = src ? src[i] : 0xffu;
+        if (tail && i == n_bytes - 1) b &= (1u << tail) - 1u;
+        d[i] |= (uint8_t)(b << sh);
+        /* a nonzero carry lies below dst_bit + n_bits: that byte exists */
+        unsigned carry = b >> (8 - sh);
+        if (carry) d[i + 1] |= (uint8_t)carry;
+    }
+}

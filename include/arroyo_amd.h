@@ -372,6 +372,43 @@ int arroyo_amd_map_process_batch_device(void *h, const int64_t *const *dcols,
                                         int32_t n_cols, int64_t n_rows,
                                         const int64_t **d_out_cols,
                                         int64_t *n_out_rows);
+/* SQL NULLs through the map (AmdMapConfig.null_semantics = 1; opcode table,
+ * propagation rules and the NULLIF idiom for a guarded division are in
+ * arroyo_amd_types.h).  These sit between the outer joins, which emit
+ * validity bitmaps, and the nullable updating aggregate, which takes them.
+ *
+ * Bitmaps are Arrow's: LSB first, bit offset 0, (n_rows + 7) / 8 bytes.
+ * `validity` may be NULL and validity[c] may be NULL: all valid.  Any
+ * column, _timestamp included, may carry one; padding bits past n_rows may
+ * hold anything.
+ *   host surface    no alignment or padding demand on the input; chunks at
+ *                   the operator's capacity.  out->validity[c] is NULL for
+ *                   a column whose emitted rows are all valid and
+ *                   out->validity itself when every column is; padding bits
+ *                   are clear; the value under a NULL is 0
+ *   device surface  each dvalidity[c] is 8-byte aligned and padded to a
+ *                   multiple of 8 bytes (read in place as 64-bit words);
+ *                   n_rows above the capacity is an error.  Every
+ *                   d_out_validity[i] is a device bitmap owned by the
+ *                   operator until the next call, 8-byte aligned, padded to
+ *                   8 bytes, padding bits clear; null_counts[i] (host) is
+ *                   the number of NULLs in emitted column i, so a
+ *                   downstream call may pass NULL for a column with 0
+ * The nullable calls on a null_semantics = 0 handle fail.  On a
+ * null_semantics = 1 handle the plain map_process_batch is legal -- every
+ * input valid -- and still fills out->validity, as NULLIF and COALESCE make
+ * NULLs of their own; the plain map_process_batch_device fails, having no
+ * way to return bitmaps. */
+int arroyo_amd_map_process_batch_nullable(void *h,
+                                          const int64_t *const *cols,
+                                          const uint8_t *const *validity,
+                                          int32_t n_cols, int64_t n_rows,
+                                          AmdOutBatch *out);
+int arroyo_amd_map_process_batch_nullable_device(
+    void *h, const int64_t *const *dcols, const uint8_t *const *dvalidity,
+    int32_t n_cols, int64_t n_rows, const int64_t **d_out_cols,
+    const uint8_t **d_out_validity, int64_t *null_counts,
+    int64_t *n_out_rows);
 void arroyo_amd_map_destroy(void *h);
 const char *arroyo_amd_map_last_error(void *h);
 

@@ -333,7 +333,48 @@ typedef struct {
  * A config is validated at create (include/arroyo_amd_map_check.h): opcodes
  * and registers in range, and every register that is read -- by an
  * instruction, out_reg[] or filter_reg -- is an input register or the dst
- * of an earlier instruction. */
+ * of an earlier instruction.
+ *
+ * SQL NULLs (AmdMapConfig.null_semantics = 1; HIP operator only, the CPU
+ * oracle rejects it at create).  Every register carries a validity bit next
+ * to its value; input validity arrives as Arrow bitmaps through
+ * arroyo_amd_map_process_batch_nullable[_device] and every output column
+ * leaves with one.  Five more opcodes exist only in such a program (with
+ * null_semantics = 0 they stay "unknown opcode"):
+ *   IS_NULL      a          1 if a is NULL, else 0; never NULL
+ *   IS_NOT_NULL  a          1 if a is valid, else 0; never NULL
+ *   COALESCE     a, b       a if a is valid, else b (NULL if both are);
+ *                           a raw 64-bit move
+ *   NULLIF       a, b       NULL if a is NULL; a if b is NULL; NULL if the
+ *                           raw i64 a == b; else a
+ *   SELECT       a, b, imm  CASE WHEN a THEN b ELSE r[imm] END: b if a is
+ *                           valid and nonzero, else register `imm`; value
+ *                           and validity of the chosen branch.  `imm` is a
+ *                           source register: 0 <= imm < AMD_MAP_MAX_REGS
+ *                           and written earlier
+ * The other opcodes under null_semantics = 1 (restated from arrow-arith /
+ * DataFusion like the arithmetic above; NOT golden-pinned, the checker is
+ * the independent reference in tests/test_mapop_null.py):
+ *   ADD..MOD EQ..GE NOT I2F F2I FADD..FDIV
+ *                NULL if any operand they read is NULL
+ *   errors       a row whose result is NULL raises none: x / NULL, NULL / 0,
+ *                NULL % 0 and F2I(NULL) are NULL (arrow-arith evaluates
+ *                valid slots only); a valid x / 0 still errors
+ *   AND          false if either side is valid-false, else NULL if either
+ *                side is NULL, else true (Kleene)
+ *   OR           true if either side is valid-true, else NULL if either
+ *                side is NULL, else false (Kleene)
+ *   CONST        always valid
+ *   filter       keeps a row iff filter_reg is valid and nonzero: a NULL
+ *                predicate drops the row
+ *   values       the value under a NULL input is arbitrary and influences
+ *                no result and no error; the value under a NULL output is
+ *                exactly 0 (the updating aggregate's convention)
+ * The machine is eager: both branches of a SELECT have already been
+ * evaluated, errors included.  A guarded division therefore divides by a
+ * NULLIF, never by the raw divisor:
+ *   SELECT(b != 0, a / NULLIF(b, 0), else)
+ * a / NULL is NULL and raises nothing, and SELECT then takes `else`. */
 enum AmdMapOp {
     AMD_MOP_CONST = 0,  /* dst = imm */
     AMD_MOP_ADD, AMD_MOP_SUB, AMD_MOP_MUL, AMD_MOP_DIV, AMD_MOP_MOD,
@@ -342,6 +383,9 @@ enum AmdMapOp {
     AMD_MOP_I2F, AMD_MOP_F2I,    /* value <-> f64 bit pattern (truncating) */
     AMD_MOP_FADD, AMD_MOP_FSUB, AMD_MOP_FMUL, AMD_MOP_FDIV
 };
+/* opcodes 21..25, legal in null_semantics = 1 programs only (table above):
+ * enum AmdMapNullOp */
+#include "arroyo_amd_map_null.h"
 
 #define AMD_MAP_MAX_PROG 64
 #define AMD_MAP_MAX_REGS 32
@@ -351,7 +395,8 @@ typedef struct {
     int32_t op;     /* AmdMapOp */
     int32_t a, b;   /* source registers (b unused for unary/CONST) */
     int32_t dst;
-    int64_t imm;    /* CONST value (f64 ops: bit pattern) */
+    int64_t imm;    /* CONST value (f64 ops: bit pattern); SELECT: the
+                       else-branch register */
 } AmdMapInstr;
 
 typedef struct {
@@ -364,6 +409,10 @@ typedef struct {
     int32_t filter_reg;         /* -1 = no filter */
     int32_t device;
     int32_t emit_to_host;
+    int32_t null_semantics;     /* 0 = no NULLs (the contract above, byte for
+                                   byte); 1 = SQL NULL semantics: a validity
+                                   bit per register, opcodes 21..25 legal,
+                                   bitmaps in and out */
 } AmdMapConfig;
 
 /* Output batch, allocated by the callee; free with *_free_out.
