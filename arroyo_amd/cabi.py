@@ -264,14 +264,39 @@ class AmdWindowFnConfig(ctypes.Structure):
         ("log2_out_cap", ctypes.c_uint32),
         ("device", ctypes.c_int32),
         ("emit_to_host", ctypes.c_int32),
+        ("fn", ctypes.c_int32),
+        ("arg_col", ctypes.c_int32),
+        ("frame", ctypes.c_int32),
+        ("offset", ctypes.c_int64),
+        ("has_default", ctypes.c_int32),
+        ("default_value", ctypes.c_int64),
     ]
+
+
+# AMD_WFN_* of include/arroyo_amd_types.h
+(WFN_ROW_NUMBER, WFN_RANK, WFN_DENSE_RANK, WFN_LAG, WFN_LEAD,
+ WFN_FIRST_VALUE, WFN_LAST_VALUE, WFN_SUM, WFN_COUNT, WFN_MIN,
+ WFN_MAX) = range(11)
+WFN_FRAME_RANGE, WFN_FRAME_ROWS, WFN_FRAME_PARTITION = range(3)
+WFN_SCAN_TILE = 2048
 
 
 def make_windowfn_config(n_cols, part_col, order, limit=0, log2_rows_cap=15,
                          instants=128, log2_out_cap=20, device=0,
-                         emit_to_host=True):
-    """order: list of (col, desc) pairs, max 2."""
+                         emit_to_host=True, fn=WFN_ROW_NUMBER, arg_col=-1,
+                         frame=WFN_FRAME_RANGE, offset=1, default=None):
+    """order: list of (col, desc) pairs, max 2.  fn: a WFN_* function over
+    the i64 column arg_col (-1 where it takes none); frame: a WFN_FRAME_*
+    for the aggregates, FIRST_VALUE and LAST_VALUE; offset and default: the
+    LAG/LEAD distance and the value where it leaves the partition (None =
+    SQL NULL).  See AmdWindowFnConfig in arroyo_amd_types.h."""
     cfg = AmdWindowFnConfig()
+    cfg.fn = fn
+    cfg.arg_col = arg_col
+    cfg.frame = frame
+    cfg.offset = offset
+    cfg.has_default = 0 if default is None else 1
+    cfg.default_value = 0 if default is None else default
     cfg.n_cols = n_cols
     cfg.part_col = part_col
     cfg.n_order = len(order)
@@ -949,11 +974,24 @@ class UpdAggOp(_Handle):
 
 
 class WindowFnOp(_Handle):
-    """One ROW_NUMBER window-function operator behind the C ABI, mirroring
+    """One window-function operator behind the C ABI, mirroring
     WindowFunctionOperator's ArrowOperator surface
     (crates/arroyo-worker/src/arrow/window_fn.rs)."""
 
     FAMILY = "windowfn_"
+
+    def __init__(self, lib, prefix, cfg):
+        if cfg.fn != WFN_ROW_NUMBER and prefix != "arroyo_amd_":
+            raise ValueError(
+                f"window function {cfg.fn}: the oracle implements "
+                "ROW_NUMBER only")
+        super().__init__(lib, prefix, cfg)
+
+    def handle_watermark_with_validity(self, wm):
+        """handle_watermark plus the per-column validity as bool masks (all
+        True for a column without a bitmap): returns (cols, masks).  Only
+        the function column of LAG/LEAD without a default holds NULLs."""
+        return self._call_out("handle_watermark", wm, with_validity=True)
 
     def process_batch(self, cols):
         self._send("process_batch", cols)

@@ -20,7 +20,8 @@ _SRCS = [os.path.join(_DIR, "csrc", f)
 # headers every source includes: editing one rebuilds the library
 _HDRS = [os.path.join(_DIR, "csrc", f) for f in ("op_common.h", "op_out.h")]
 _HDRS += [os.path.join(_DIR, "..", "include", f)
-          for f in ("arroyo_amd_map_check.h", "arroyo_amd_map_null.h")]
+          for f in ("arroyo_amd_types.h", "arroyo_amd_map_check.h",
+                    "arroyo_amd_map_null.h")]
 
 _lib = None
 

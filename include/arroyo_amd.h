@@ -326,19 +326,28 @@ int arroyo_amd_updagg_restore(void *h, int32_t which,
 void arroyo_amd_updagg_destroy(void *h);
 const char *arroyo_amd_updagg_last_error(void *h);
 
-/* ---- SQL window function (ROW_NUMBER per instant) ---------------------
+/* ---- SQL window functions (per instant) -------------------------------
  * Replaces WindowFunctionOperator
  * (crates/arroyo-worker/src/arrow/window_fn.rs) behind the same
  * ArrowOperator surface:
- *   windowfn_create           <-> WindowFunctionConstructor (:180-273)
+ *   windowfn_create           <-> WindowFunctionConstructor (:180-273);
+ *                                 AmdWindowFnConfig.fn picks the function
+ *                                 (AMD_WFN_*: ROW_NUMBER, RANK, DENSE_RANK,
+ *                                 LAG, LEAD, FIRST_VALUE, LAST_VALUE, SUM,
+ *                                 COUNT, MIN, MAX), .frame its frame; the
+ *                                 CPU oracle implements ROW_NUMBER only
  *   windowfn_process_batch    <-> process_batch (:275-300): buffers rows
  *                                 per exact instant; late rows silently
  *                                 filtered (filter_and_split_batches)
  *   windowfn_handle_watermark <-> handle_watermark (:220-246): fires
  *                                 instants < wm in timestamp order; out
- *                                 columns [input cols..., row_number]
+ *                                 columns [input cols..., function value];
+ *                                 LAG/LEAD without a default set
+ *                                 out->validity of the function column
+ *                                 where a NULL occurs
  *   windowfn_checkpoint_drain <-> handle_checkpoint (:302-324): buffered
- *                                 rows; restore = process_batch
+ *                                 rows in arrival order; restore =
+ *                                 process_batch
  */
 void *arroyo_amd_windowfn_create(const AmdWindowFnConfig *cfg);
 int arroyo_amd_windowfn_process_batch(void *h, const int64_t *const *cols,

@@ -272,17 +272,67 @@ typedef struct {
                                    value under a NULL is 0 */
 } AmdUpdatingConfig;
 
-/* SQL window-function (ROW_NUMBER) configuration.  Mirrors
+/* SQL window-function configuration.  Mirrors
  * api::WindowFunctionOperator as decoded by WindowFunctionConstructor
  * (crates/arroyo-worker/src/arrow/window_fn.rs:180-273): a
  * BoundedWindowAggExec run per exact `_timestamp` instant.  Semantics
  * (filter_and_split_batches :52-93, handle_watermark :220-246): rows are
  * buffered per instant (late rows ts < watermark silently filtered); when
  * the watermark passes an instant it fires in timestamp order, computing
- * ROW_NUMBER() OVER (PARTITION BY part_col ORDER BY order cols) per row;
- * rows with row_number > limit are dropped (the reference plans the
- * downstream filter separately; fusing it here saves materialising the
- * full ranking).  Output columns: input columns + trailing row_number. */
+ * fn(...) OVER (PARTITION BY part_col ORDER BY order cols <frame>) per row;
+ * with a limit, rows whose function value is > limit are dropped (the
+ * reference plans the downstream filter separately; fusing it here saves
+ * materialising the full ranking).  Output columns: input columns +
+ * trailing function value.
+ *
+ * The fields from `fn` on were appended: all zero they are ROW_NUMBER,
+ * exactly the operator before them (the CPU oracle reads none of them and
+ * numbers rows whatever they say).
+ *
+ * The functions (restated from DataFusion 48's window functions, whose
+ * sources are not in the reference tree: NOT golden-pinned, the checker is
+ * the independent restatement in tests/test_windowfn_funcs.py).  Rows sort
+ * by partition, ORDER BY columns, arrival; peers are rows of one partition
+ * equal on every ORDER BY column.  For the row at 0-based position t of a
+ * partition of m rows, whose peer group spans positions ps..pe:
+ *   ROW_NUMBER   t + 1
+ *   RANK         ps + 1
+ *   DENSE_RANK   peer groups up to and including its own
+ *   LAG(arg, k)  arg at t - k if t - k >= 0, else default_value if
+ *                has_default, else SQL NULL; k = 0 is the row's own value
+ *   LEAD(arg, k) the same with t + k < m
+ *   frame end e  t (ROWS), pe (RANGE), m - 1 (PARTITION); the frame always
+ *                starts at position 0
+ *   FIRST_VALUE  arg at 0            LAST_VALUE  arg at e
+ *   SUM MIN MAX  over positions 0..e; SUM wraps in two's complement
+ *   COUNT        e + 1
+ * `arg` is a non-nullable i64 column.  NULLs (LAG/LEAD without a default)
+ * leave through AmdOutBatch.validity of the function column, the value
+ * under a NULL is 0; a batch without a NULL carries no validity table.
+ * With limit == 0 a fired instant's rows come out in sort order
+ * (partition, ORDER BY, arrival), instants in timestamp order.
+ *
+ * Rejected at create, each with its own message: an unknown fn or frame;
+ * arg_col outside [0, n_cols - 2] for LAG LEAD FIRST_VALUE LAST_VALUE SUM
+ * MIN MAX (COUNT also takes -1), arg_col != -1 for RANK and DENSE_RANK
+ * (ROW_NUMBER takes -1 or the 0 of a zeroed tail); offset < 0; limit != 0
+ * with anything but ROW_NUMBER RANK DENSE_RANK; frame != 0 for
+ * ROW_NUMBER, the rank functions and LAG/LEAD, which ignore frames. */
+enum {
+    AMD_WFN_ROW_NUMBER = 0, AMD_WFN_RANK, AMD_WFN_DENSE_RANK, AMD_WFN_LAG,
+    AMD_WFN_LEAD, AMD_WFN_FIRST_VALUE, AMD_WFN_LAST_VALUE, AMD_WFN_SUM,
+    AMD_WFN_COUNT, AMD_WFN_MIN, AMD_WFN_MAX
+};
+enum {
+    AMD_WFN_FRAME_RANGE = 0,      /* RANGE UNBOUNDED PRECEDING .. CURRENT ROW,
+                                     peers included: DataFusion's default
+                                     under an ORDER BY */
+    AMD_WFN_FRAME_ROWS = 1,       /* ROWS UNBOUNDED PRECEDING .. CURRENT ROW */
+    AMD_WFN_FRAME_PARTITION = 2   /* unbounded on both ends */
+};
+/* rows one block of the segmented-scan kernels covers per tile */
+#define AMD_WFN_SCAN_TILE 2048
+
 typedef struct {
     int32_t  n_cols;          /* input columns incl. trailing _timestamp */
     int32_t  part_col;        /* partition column index; -1 = whole instant */
@@ -295,6 +345,17 @@ typedef struct {
     uint32_t log2_out_cap;
     int32_t  device;
     int32_t  emit_to_host;
+    int32_t  fn;              /* AMD_WFN_*; 0 = ROW_NUMBER */
+    int32_t  arg_col;         /* the function's value column; -1 = none */
+    int32_t  frame;           /* AMD_WFN_FRAME_*; aggregates, FIRST_VALUE
+                                 and LAST_VALUE only */
+    int64_t  offset;          /* LAG/LEAD distance k >= 0, taken as it
+                                 stands: 0 is the row's own value (SQL's
+                                 default distance of 1 is supplied by
+                                 whoever fills the config, as
+                                 cabi.make_windowfn_config does) */
+    int32_t  has_default;     /* LAG/LEAD: default_value instead of NULL */
+    int64_t  default_value;
 } AmdWindowFnConfig;
 
 /* Stateless map/filter/projection configuration.  Replaces the reference's
