@@ -404,6 +404,37 @@ def make_strkey_config(log2_capacity=16, arena_bytes=1 << 24, hash_bits=0,
     return cfg
 
 
+# ---- device tuple-key dictionary (arroyo_amd_tuplekey_*) -------------------
+
+AMD_TKEY_MAX_COLS = 8
+AMD_TKEY_BLOCK_THREADS = 256
+AMD_TKEY_MAX_BLOCKS = 2048
+# rows one pass of the largest grid covers; one more runs the stride loop twice
+TKEY_GRID_ROWS = AMD_TKEY_BLOCK_THREADS * AMD_TKEY_MAX_BLOCKS
+TKEY_MAX_ROWS = 2**31 - 2
+
+
+class AmdTupleKeyConfig(ctypes.Structure):
+    _fields_ = [
+        ("device", ctypes.c_int32),
+        ("n_cols", ctypes.c_int32),
+        ("log2_capacity", ctypes.c_int32),
+        ("hash_bits", ctypes.c_int32),
+        ("nullable", ctypes.c_int32),
+    ]
+
+
+def make_tuplekey_config(n_cols, log2_capacity=16, hash_bits=0,
+                         nullable=False, device=0):
+    cfg = AmdTupleKeyConfig()
+    cfg.device = device
+    cfg.n_cols = n_cols
+    cfg.log2_capacity = log2_capacity
+    cfg.hash_bits = hash_bits
+    cfg.nullable = 1 if nullable else 0
+    return cfg
+
+
 # ---- keyed shuffle: stable device partition (arroyo_amd_shuffle_*) --------
 
 AMD_SHUF_KEY_I64 = 0    # owner from splitmix64 of the key column
@@ -483,7 +514,7 @@ _FAMILIES = {   # symbol infix -> config struct of its create
     "session_": AmdSessionConfig, "expjoin_": AmdExpJoinConfig,
     "updagg_": AmdUpdatingConfig, "windowfn_": AmdWindowFnConfig,
     "map_": AmdMapConfig, "strkey_": AmdStrKeyConfig,
-    "shuffle_": AmdShuffleConfig,
+    "shuffle_": AmdShuffleConfig, "tuplekey_": AmdTupleKeyConfig,
 }
 
 _INT_PROTOTYPES = {
@@ -554,6 +585,15 @@ _INT_PROTOTYPES = {
     "strkey_checkpoint_drain": (_vp, _strs),
     "strkey_restore": (_vp, _vp, _vp, _vp, _i64),
     "strkey_profile": (_vp, _int, _P(_dbl)),
+    # tuple-key dictionary (column / bitmap tables, buffers as raw addresses)
+    "tuplekey_encode": (_vp, _cols, _cols, _i64, _vp, _vp),
+    "tuplekey_encode_device": (_vp, _cols, _cols, _i64, _vp, _vp),
+    "tuplekey_hash_device": (_vp, _cols, _cols, _i64, _vp),
+    "tuplekey_decode": (_vp, _vp, _i64, _out),
+    "tuplekey_decode_device": (_vp, _vp, _i64, _cols, _cols),
+    "tuplekey_count": (_vp, _P(_i64)),
+    "tuplekey_checkpoint_drain": _OUT,
+    "tuplekey_restore": (_vp, _vp, _cols, _cols, _i64),
     # keyed shuffle
     "shuffle_partition_device": (_vp, _cols, _vp, _vp, _i64,
                                  _P(AmdShuffleOut)),
@@ -1197,3 +1237,145 @@ class StrKeyDict(_Handle):
         used = ctypes.c_int64(0)
         self._call("count", None, ctypes.byref(used))
         return int(used.value)
+
+
+# ---- the tuple-key dictionary ------------------------------------------------
+
+def _words(col):
+    """An 8-byte column (i64, u64, f64) as the contiguous int64 view of its
+    raw bits."""
+    col = np.ascontiguousarray(col)
+    if col.dtype.itemsize != 8 or col.ndim != 1:
+        raise ValueError("tuple components are 1-D columns of 8-byte elements")
+    return col.view(np.int64)
+
+
+def _out_masks(out):
+    """The validity of an AmdOutBatch as it stands: None when the batch has
+    no validity table, else a list with None for a column without a bitmap
+    and a bool mask (True = non-null) otherwise."""
+    return out_validity(out) if out.validity else None
+
+
+class TupleKeyDict(_Handle):
+    """Device-resident interner for composite and nullable keys behind the
+    C ABI: tuples of up to 8 64-bit words, each optionally NULL, in; stable
+    non-negative int64 ids out (and back).  Share one instance between every
+    operator that must agree on the ids."""
+
+    FAMILY = "tuplekey_"
+
+    def _host_batch(self, cols, valid):
+        """(arrays to hold, column table, bitmap table, rows) of a host
+        batch.  valid is None or a list parallel to cols of None (column all
+        valid), a bool mask (True = non-null) or an already packed Arrow
+        bitmap (uint8, at least (rows + 7) // 8 bytes)."""
+        if len(cols) != self.cfg.n_cols:
+            raise ValueError(
+                f"{len(cols)} columns for a handle of {self.cfg.n_cols}")
+        keep = [_words(c) for c in cols]
+        n = len(keep[0])
+        if any(len(c) != n for c in keep):
+            raise ValueError("columns differ in length")
+        varr = None
+        if valid is not None:
+            if len(valid) != len(cols):
+                raise ValueError(
+                    f"valid has {len(valid)} entries for {len(cols)} cols")
+            ptrs = []
+            for m in valid:
+                if m is None:
+                    ptrs.append(None)
+                    continue
+                m = np.asarray(m)
+                if m.dtype == np.uint8:
+                    bm = np.ascontiguousarray(m)
+                    if len(bm) < (n + 7) // 8:
+                        raise ValueError("packed bitmap shorter than "
+                                         "(n_rows + 7) // 8 bytes")
+                else:
+                    if len(m) != n:
+                        raise ValueError("validity mask length != n_rows")
+                    bm = pack_validity(m)
+                if len(bm) == 0:
+                    bm = np.zeros(1, dtype=np.uint8)
+                keep.append(bm)
+                ptrs.append(bm.ctypes.data)
+            varr = _ptr_array(ptrs)
+        return keep, _ptr_array([c.ctypes.data for c in keep[:len(cols)]]), \
+            varr, n
+
+    def _call_tuples(self, name, *args):
+        """Call a function whose last parameter is an AmdOutBatch*; return
+        (cols, masks) with masks as _out_masks gives them."""
+        out = AmdOutBatch()
+        self._call(name, *args, ctypes.byref(out))
+        cols, masks = _out_to_numpy(out), _out_masks(out)
+        self._fn["free_out"](ctypes.byref(out))
+        return cols, masks
+
+    def encode(self, cols, valid=None, want_hashes=False):
+        """Host columns (and validity) -> int64 ids (and uint64 content
+        hashes when want_hashes)."""
+        keep, carr, varr, n = self._host_batch(cols, valid)
+        ids = np.empty(n, dtype=np.int64)
+        hashes = np.empty(n, dtype=np.uint64) if want_hashes else None
+        self._call("encode", carr, varr, n, ids.ctypes.data,
+                   hashes.ctypes.data if want_hashes else None)
+        return (ids, hashes) if want_hashes else ids
+
+    @staticmethod
+    def _dev_tables(d_cols, d_valid):
+        if d_valid is not None and len(d_valid) != len(d_cols):
+            raise ValueError(
+                f"d_valid has {len(d_valid)} entries for {len(d_cols)} cols")
+        return _ptr_array(d_cols), \
+            None if d_valid is None else _ptr_array(d_valid)
+
+    def encode_device(self, d_cols, d_valid, n, d_ids, d_hashes=None):
+        """Device addresses (ints) in: d_cols one per component, d_valid
+        None or a list of None / addresses of 8-byte aligned bitmaps padded
+        to 8 bytes.  Ids (and hashes) are written on the device;
+        synchronised on return."""
+        carr, varr = self._dev_tables(d_cols, d_valid)
+        self._call("encode_device", carr, varr, n, d_ids, d_hashes)
+
+    def hash_device(self, d_cols, d_valid, n, d_hashes):
+        """The content hash alone; touches no table state."""
+        carr, varr = self._dev_tables(d_cols, d_valid)
+        self._call("hash_device", carr, varr, n, d_hashes)
+
+    def decode(self, ids):
+        """int64 ids -> (cols, masks): n_cols int64 columns of raw words (0
+        under a NULL); masks is None when no decoded component is NULL, else
+        a list with a bool mask (True = non-null) for exactly the columns
+        that hold one and None for the others."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        return self._call_tuples("decode", ids.ctypes.data, len(ids))
+
+    def decode_device(self, d_ids, n, d_cols_out, d_valid_out=None):
+        """Device ids -> device columns and, on a nullable handle, validity
+        words ((n + 63) // 64 uint64 per column, written in full)."""
+        carr, varr = self._dev_tables(d_cols_out, d_valid_out)
+        self._call("decode_device", d_ids, n, carr, varr)
+
+    def count(self):
+        """Number of interned tuples."""
+        n = ctypes.c_int64(0)
+        self._call("count", ctypes.byref(n))
+        return int(n.value)
+
+    def drain(self):
+        """Checkpoint: every interned tuple -> (ids, cols, masks), cols and
+        masks as decode returns them."""
+        cols, masks = self._call_tuples("checkpoint_drain")
+        return cols[0], cols[1:], None if masks is None else masks[1:]
+
+    def restore(self, ids, cols, valid=None):
+        """Load a drain() into this (empty) handle; every tuple keeps its
+        id."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        keep, carr, varr, n = self._host_batch(cols, valid)
+        if len(ids) != n:
+            raise ValueError("ids and cols disagree on the row count")
+        self._call("restore", ids.ctypes.data, carr, varr, n)

@@ -16,7 +16,7 @@ _SO = os.path.join(_DIR, "libarroyo_amd.so")
 _SRCS = [os.path.join(_DIR, "csrc", f)
          for f in ("arroyo_amd.hip", "join.hip", "session.hip", "expjoin.hip",
                    "updagg.hip", "windowfn.hip", "mapop.hip", "strkey.hip",
-                   "shuffle.hip")]
+                   "shuffle.hip", "tuplekey.hip")]
 # headers every source includes: editing one rebuilds the library
 _HDRS = [os.path.join(_DIR, "csrc", f) for f in ("op_common.h", "op_out.h")]
 _HDRS += [os.path.join(_DIR, "..", "include", f)
@@ -139,6 +139,11 @@ def make_map_op(cfg):
 def make_strkey(cfg):
     from arroyo_amd.cabi import StrKeyDict
     return StrKeyDict(lib(), "arroyo_amd_", cfg)
+
+
+def make_tuplekey(cfg):
+    from arroyo_amd.cabi import TupleKeyDict
+    return TupleKeyDict(lib(), "arroyo_amd_", cfg)
 
 
 class Shuffler(_Handle):

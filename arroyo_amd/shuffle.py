@@ -33,6 +33,35 @@ def splitmix64_np(x):
     return x ^ (x >> U64(31))
 
 
+def tuple_hash_np(cols, valid=None):
+    """The content hash of the tuple-key dictionary (arroyo_amd_tuplekey_*),
+    restated in numpy: h = splitmix64(mask), then h = splitmix64(h ^ w_c)
+    for every component in order, with bit c of mask set and w_c = 0 where
+    component c is NULL.  cols: equal-length 8-byte numpy columns, taken as
+    raw bits; valid: None or a list parallel to cols of None (all valid) /
+    bool masks (True = non-null).  The sending side of a keyed shuffle can
+    hash on the host with it and partition in KEY_HASH mode."""
+    words = []
+    for c in cols:
+        c = np.ascontiguousarray(c)
+        if c.dtype.itemsize != 8:
+            raise ValueError("tuple components are 8-byte elements")
+        words.append(c.view(U64))
+    n = len(words[0]) if words else 0
+    mask = np.zeros(n, dtype=U64)
+    for i, w in enumerate(words):
+        if valid is None or valid[i] is None:
+            continue
+        null = ~np.asarray(valid[i], dtype=bool)
+        mask |= null.astype(U64) << U64(i)
+        words[i] = np.where(null, U64(0), w)
+    with np.errstate(over="ignore"):
+        h = splitmix64_np(mask)
+        for w in words:
+            h = splitmix64_np(h ^ w)
+    return h
+
+
 def partition_ids(keys, n_parts):
     """Owner rank per row: hash / (2^64 / n) — contiguous hash ranges, same
     scheme as server_for_hash (arroyo-types:640-647)."""

@@ -470,8 +470,10 @@ const char *arroyo_amd_map_last_error(void *h);
  * needs the same log2_capacity and hash_bits; a mismatch is an error and
  * leaves the handle empty.
  *
- * Out of scope: LargeUtf8 (int64 offsets); NULL keys (no validity bitmap is
- * accepted, as with every other family); eviction (ids must stay stable for
+ * Out of scope: LargeUtf8 (int64 offsets); NULL keys here (no validity
+ * bitmap is accepted: a nullable string key goes through the tuple-key
+ * dictionary below, its strkey id as the component and its validity bitmap
+ * alongside); eviction (ids must stay stable for
  * live state, as for the composite-key dictionary); the oracle has no
  * counterpart -- a host dictionary is the checker for an interner. */
 void *arroyo_amd_strkey_create(const AmdStrKeyConfig *cfg);
@@ -497,6 +499,130 @@ int arroyo_amd_strkey_profile(void *h, int enable, double *last_lookup_ms);
 void arroyo_amd_strkey_free_out(AmdStrBatch *out);
 void arroyo_amd_strkey_destroy(void *h);
 const char *arroyo_amd_strkey_last_error(void *h);
+
+/* ---- device tuple-key dictionary: composite and NULL keys -----------------
+ * Every keyed operator above takes one non-nullable i64 key column; the
+ * reference keys its state on the row-encoded key tuple
+ * (crates/arroyo-state/src/tables/expiring_time_key_map.rs:1008-1049), any
+ * number of columns, a SQL NULL being one more key value.  This family
+ * interns a tuple of n_cols (1..AMD_TKEY_MAX_COLS) 64-bit words, each with
+ * an optional Arrow validity bit, on device: every tuple maps to an opaque,
+ * stable, non-negative i64 id that any operator above accepts as its single
+ * key column, and ids map back to columns and validity at emission.  It
+ * sits in front of and behind the other operators exactly as the string-key
+ * dictionary does, and no engine changes.  One handle is shared by every
+ * operator that must agree on the ids (both sides of a join).  A strkey id
+ * is a legal component: GROUP BY event_type, driver_id on raw strings is
+ * strkey_encode, then tuplekey_encode over (string id, driver_id), the
+ * operator, tuplekey_decode, then strkey_decode of the first component.
+ *
+ *   tuplekey_encode / _device  <-> the key row-encoding ahead of process_batch
+ *   tuplekey_decode / _device  <-> rebuilding the key columns of an emission
+ *   tuplekey_hash_device       <-> the key hash of the sending side of a
+ *                                  keyed shuffle
+ *   tuplekey_checkpoint_drain / tuplekey_restore
+ *                              <-> part of the keyed operators' checkpoint:
+ *                                  their drained state refers to these ids
+ *
+ * Columns: `cols` is n_cols pointers to columns of n_rows 8-byte elements.
+ * `validity` is NULL (nothing is NULL) or n_cols pointers, each NULL (column
+ * all valid) or an Arrow validity bitmap, LSB order, bit offset 0, of
+ * (n_rows + 7) / 8 bytes; no byte past that is read and bits at positions
+ * >= n_rows influence nothing.  A bitmap on a handle created with
+ * nullable = 0 is an error.  On the device surface the pointer tables are
+ * host arrays of device addresses, and a device bitmap is 8-byte aligned and
+ * padded to a multiple of 8 bytes (the *_nullable_device convention).
+ *
+ * Identity: two tuples are equal iff their null masks are equal (one byte,
+ * bit c set when component c is NULL) and their words are equal at every
+ * non-NULL position.  The word under a NULL is never read, neither for
+ * identity nor for the hash, and is stored and decoded as 0.  Words compare
+ * as raw 64-bit patterns: for an f64 column -0.0 and 0.0 are different keys,
+ * and two NaNs are one key only if their bits agree.  (NULL, 0), (0, NULL)
+ * and (0, 0) are three keys.  Ids are opaque; callers may assume only
+ * id >= 0 (never the engines' EMPTY_KEY), for the life of the handle and
+ * across batches.
+ *
+ * Hash: hashes_out / d_hashes_out may be NULL; otherwise they receive the
+ * 64-bit content hash per row,
+ *   h = splitmix64(mask); for c in 0 .. n_cols - 1: h = splitmix64(h ^ w_c)
+ * with w_c = 0 under a NULL and splitmix64 the finaliser arroyo_amd_partition
+ * uses; shuffle.tuple_hash_np restates the hash in numpy.  It is
+ * identical across handles, devices and hash_bits.  Ids are per handle, so a
+ * keyed shuffle partitions on this hash (AMD_SHUF_KEY_HASH), never on ids;
+ * tuplekey_hash_device computes it alone and touches no table state.  For a
+ * Utf8 component the sender passes strkey's content-hash column as that
+ * component: string ids differ per GPU, the content hash does not.
+ *
+ * Joins: SQL GROUP BY and PARTITION BY put all NULLs in one group, which is
+ * what the identity above gives.  An equi-join never matches a NULL key: the
+ * caller of a join drops rows with a NULL key component before encode (the
+ * map operator's IS_NOT_NULL filter) or routes them to the unmatched output.
+ * The dictionary does not decide that.
+ *
+ * encode: n_rows is at most 2^31 - 2 per call (more is an error);
+ * n_rows == 0 succeeds and does nothing.  Rows of one batch that hold the
+ * same new tuple get the same id in that call.
+ *
+ * decode returns n_cols host columns in `out` (free with
+ * arroyo_amd_free_out).  out->validity is NULL when no decoded component is
+ * NULL; otherwise it is a table with a bitmap for exactly the columns that
+ * hold a NULL.  decode_device writes n_cols device columns and, on a
+ * nullable = 1 handle, n_cols device bitmaps of (n_rows + 63) / 64 64-bit
+ * words each, written in full, bits past n_rows clear; d_validity_out is
+ * NULL on a nullable = 0 handle and required otherwise.  It is for chaining
+ * behind an operator with emit_to_host = 0.  An id that is negative, out of
+ * range or was never issued is an error.
+ *
+ * Capacity: at most 7/8 of the slots are used.  An encode that would pass
+ * that fails ("capacity"); tuples interned by earlier calls stay valid, the
+ * failing call's ids_out are undefined and its claimed slots are retired.
+ *
+ * checkpoint_drain returns every interned tuple: column 0 the ids, then the
+ * n_cols components, validity by the rule of decode.  restore loads that
+ * into an EMPTY handle (anything else is an error) so every tuple keeps its
+ * id.  An id is a slot of the hash table, so the restoring handle needs the
+ * same n_cols, log2_capacity, hash_bits and nullable; an id out of range or
+ * not reachable from its tuple's home slot, or a bitmap on a nullable = 0
+ * handle, is an error and leaves the handle empty.  n_cols is the length of
+ * the `cols` table and cannot be checked by the callee.
+ *
+ * The device surface takes device pointers, runs on the handle's own stream
+ * and synchronises before returning, so a chained *_process_batch_device on
+ * another handle may consume d_ids_out directly.  A call allocates no device
+ * memory beyond what create sized, except that the per-batch scratch grows
+ * with n_rows.  One call at a time per handle.
+ *
+ * Out of scope: eviction (ids must stay stable for live state);
+ * variable-width components other than through strkey ids; more than
+ * AMD_TKEY_MAX_COLS columns; bit offsets into a bitmap; the window engine's
+ * embedded composite-key dictionary is unchanged and nothing switches over
+ * to this family silently; the oracle has no counterpart -- a host
+ * dictionary is the checker for an interner. */
+void *arroyo_amd_tuplekey_create(const AmdTupleKeyConfig *cfg);
+int arroyo_amd_tuplekey_encode(void *h, const void *const *cols,
+                               const uint8_t *const *validity, int64_t n_rows,
+                               int64_t *ids_out, uint64_t *hashes_out);
+int arroyo_amd_tuplekey_encode_device(void *h, const void *const *d_cols,
+                                      const uint8_t *const *d_validity,
+                                      int64_t n_rows, int64_t *d_ids_out,
+                                      uint64_t *d_hashes_out);
+int arroyo_amd_tuplekey_hash_device(void *h, const void *const *d_cols,
+                                    const uint8_t *const *d_validity,
+                                    int64_t n_rows, uint64_t *d_hashes_out);
+int arroyo_amd_tuplekey_decode(void *h, const int64_t *ids, int64_t n_rows,
+                               AmdOutBatch *out);
+int arroyo_amd_tuplekey_decode_device(void *h, const int64_t *d_ids,
+                                      int64_t n_rows, void *const *d_cols_out,
+                                      uint64_t *const *d_validity_out);
+int arroyo_amd_tuplekey_count(void *h, int64_t *n_tuples);
+int arroyo_amd_tuplekey_checkpoint_drain(void *h, AmdOutBatch *out);
+int arroyo_amd_tuplekey_restore(void *h, const int64_t *ids,
+                                const void *const *cols,
+                                const uint8_t *const *validity,
+                                int64_t n_rows);
+void arroyo_amd_tuplekey_destroy(void *h);
+const char *arroyo_amd_tuplekey_last_error(void *h);
 
 /* ---- keyed shuffle: stable device partition ------------------------------
  * The reference repartitions a batch between subtasks by sorting it by

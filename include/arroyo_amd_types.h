@@ -526,6 +526,33 @@ typedef struct {
     uint8_t *data;           /* [offsets[n_rows]] */
 } AmdStrBatch;
 
+/* Device tuple-key dictionary configuration (arroyo_amd_tuplekey_*).  The
+ * reference row-encodes the whole key tuple (expiring_time_key_map.rs
+ * :1008-1049, as above): any number of columns, a SQL NULL being one more
+ * key value.  Here a tuple of n_cols 64-bit words (i64, u64, f64 bit
+ * patterns, strkey ids), each optionally NULL, is interned on device to a
+ * stable non-negative i64 id that every operator above accepts as its
+ * single key column.  At most 7/8 of the 1 << log2_capacity slots are used;
+ * a slot takes 8 * (n_cols + 2) bytes of device memory. */
+#define AMD_TKEY_MAX_COLS 8
+/* the launch shape of the per-row kernels: blocks of AMD_TKEY_BLOCK_THREADS
+ * threads, at most AMD_TKEY_MAX_BLOCKS of them, grid-stride over the rows.
+ * Row counts around their product are edge cases of the kernels. */
+#define AMD_TKEY_BLOCK_THREADS 256
+#define AMD_TKEY_MAX_BLOCKS 2048
+
+typedef struct {
+    int32_t device;
+    int32_t n_cols;          /* components per tuple, 1..AMD_TKEY_MAX_COLS */
+    int32_t log2_capacity;   /* hash slots = 1 << log2_capacity (1..30) */
+    int32_t hash_bits;       /* as AmdStrKeyConfig.hash_bits: 0 = the full
+                              * 64-bit hash, k in 1..63 = only its low k bits
+                              * for slot choice AND tag (forces collisions) */
+    int32_t nullable;        /* 0: no validity bitmap is accepted or
+                              * returned; 1: every component may carry an
+                              * Arrow validity bitmap, in and out */
+} AmdTupleKeyConfig;
+
 /* Device keyed shuffle (arroyo_amd_shuffle_*): the stable partition ahead of
  * the cross-rank exchange (the reference's repartition, crates/
  * arroyo-operator/src/context.rs:506-560).  Every device buffer of a handle
