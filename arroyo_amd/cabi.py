@@ -224,15 +224,18 @@ class AmdUpdatingConfig(ctypes.Structure):
         ("log2_out_cap", ctypes.c_uint32),
         ("device", ctypes.c_int32),
         ("emit_to_host", ctypes.c_int32),
+        ("val_is_f64", ctypes.c_int32 * 8),
         ("null_semantics", ctypes.c_int32),
     ]
 
 
 def make_updagg_config(aggs, n_keys=1, n_value_cols=0, log2_capacity=16,
                        log2_nodes=20, log2_out_cap=20, device=0,
-                       emit_to_host=True, null_semantics=False):
+                       emit_to_host=True, null_semantics=False,
+                       val_is_f64=()):
     """null_semantics=True: SQL NULL semantics (nullable value columns in,
-    validity bitmaps out; see AmdUpdatingConfig in arroyo_amd_types.h)."""
+    validity bitmaps out; see AmdUpdatingConfig in arroyo_amd_types.h).
+    val_is_f64: indices of value columns holding f64 bit patterns."""
     cfg = AmdUpdatingConfig()
     cfg.n_keys = n_keys
     cfg.n_value_cols = n_value_cols
@@ -248,6 +251,8 @@ def make_updagg_config(aggs, n_keys=1, n_value_cols=0, log2_capacity=16,
     cfg.device = device
     cfg.emit_to_host = 1 if emit_to_host else 0
     cfg.null_semantics = 1 if null_semantics else 0
+    for v in val_is_f64:
+        cfg.val_is_f64[v] = 1
     return cfg
 
 

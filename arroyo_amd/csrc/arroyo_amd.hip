@@ -89,29 +89,8 @@ __host__ __device__ inline int64_t dec_max(uint64_t e) {
     return (int64_t)(e ^ 0x8000000000000000ULL);
 }
 
-/* order-preserving f64 <-> u64 with the all-zero bit pattern as identity:
- * flip maps ordered (non-NaN) doubles onto (0x000F.., 0xFFF0..] of u64, so
- * a memset-zero state is below every real encoding (MAX) and, negated,
- * above every real one (MIN) — same memset-retirable property as the i64
- * encodes. */
-__host__ __device__ inline uint64_t f64flip(uint64_t b) {
-    return (b & 0x8000000000000000ULL) ? ~b : (b | 0x8000000000000000ULL);
-}
-__host__ __device__ inline uint64_t f64unflip(uint64_t e) {
-    return (e & 0x8000000000000000ULL) ? (e & ~0x8000000000000000ULL) : ~e;
-}
-__host__ __device__ inline uint64_t enc_minf(int64_t bits) {
-    return ~f64flip((uint64_t)bits);
-}
-__host__ __device__ inline int64_t dec_minf(uint64_t e) {
-    return (int64_t)f64unflip(~e);
-}
-__host__ __device__ inline uint64_t enc_maxf(int64_t bits) {
-    return f64flip((uint64_t)bits);
-}
-__host__ __device__ inline int64_t dec_maxf(uint64_t e) {
-    return (int64_t)f64unflip(e);
-}
+/* the f64 encodings (enc_minf .. dec_maxf) are op_common.h's, shared with
+ * the updating aggregate */
 
 /* encode one raw (i64 or f64-bits) value into the op's state domain */
 __host__ __device__ inline uint64_t enc_word(int op, int isf, int64_t raw) {

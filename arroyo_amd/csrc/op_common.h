@@ -60,6 +60,33 @@ __device__ inline int64_t table_upsert(int64_t *keys, uint32_t C, int64_t key,
     return -1;
 }
 
+/* order-preserving f64 <-> u64 with the all-zero bit pattern as identity:
+ * flip maps ordered (non-NaN) doubles onto (0x000F.., 0xFFF0..] of u64, so
+ * a memset-zero state is below every real encoding (MAX) and, negated,
+ * above every real one (MIN) — same memset-retirable property as the i64
+ * encodes.  Over all bit patterns the order is IEEE totalOrder (-NaN < -inf
+ * < ... < -0.0 < +0.0 < ... < +inf < +NaN, NaNs by payload), and the zero
+ * state decodes to the one NaN pattern whose encoding is 0 (0xFFFF..FF for
+ * MAX, 0x7FFF..FF for MIN), so every pattern round-trips. */
+__host__ __device__ inline uint64_t f64flip(uint64_t b) {
+    return (b & 0x8000000000000000ULL) ? ~b : (b | 0x8000000000000000ULL);
+}
+__host__ __device__ inline uint64_t f64unflip(uint64_t e) {
+    return (e & 0x8000000000000000ULL) ? (e & ~0x8000000000000000ULL) : ~e;
+}
+__host__ __device__ inline uint64_t enc_minf(int64_t bits) {
+    return ~f64flip((uint64_t)bits);
+}
+__host__ __device__ inline int64_t dec_minf(uint64_t e) {
+    return (int64_t)f64unflip(~e);
+}
+__host__ __device__ inline uint64_t enc_maxf(int64_t bits) {
+    return f64flip((uint64_t)bits);
+}
+__host__ __device__ inline int64_t dec_maxf(uint64_t e) {
+    return (int64_t)f64unflip(e);
+}
+
 /* ------------------------------------------------------------------ */
 /* host side                                                           */
 

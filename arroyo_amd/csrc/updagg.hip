@@ -50,6 +50,18 @@
  *     the non-nullable kernels run, instantiated from the same source.
  *     The C oracle has no NULLs: tests/test_null_aggs.py compares against
  *     a Python model of DataFusion's accumulator rule.
+ *   - Float64 value columns are opt-in per column
+ *     (AmdUpdatingConfig.val_is_f64): the column's i64 plane holds f64 bit
+ *     patterns.  An operator with a flagged column runs the *_f64 kernels,
+ *     instantiated from the same source: SUM / AVG and the moment words
+ *     fold with the hardware f64 atomic add, MIN / MAX and the order
+ *     statistics use op_common.h's totalOrder encoding (so the radix
+ *     select is unchanged), and a flush that finds a key empty zeroes its
+ *     f64 sum words.  The rules are restated from DataFusion 48 /
+ *     arrow-arith, not golden-pinned: the checker is the Python model
+ *     tests/updagg_f64_ref.py (tests/test_updagg_f64.py).  Drain / restore
+ *     carry state words raw; restoring into an operator with other flags
+ *     is the caller's error.
  *
  * Parity is pinned against oracle/arroyo_oracle.c (itself pinned against
  * the reference's debezium_agg / filter_updating_aggregates golden
@@ -88,7 +100,14 @@ struct AggSpec {
     int32_t col2[AMD_MAX_AGGS];  /* co-moment family second argument */
     int32_t soff[AMD_MAX_AGGS];  /* agg a's state words at st[soff[a]..] */
     int32_t SW;                  /* total state words per key */
+    uint32_t f64m;               /* bit c: value column c holds f64 bit
+                                    patterns; read by the F64 kernels only */
 };
+
+/* aggregate a's argument (col) / second argument (col2) column is f64 */
+__host__ __device__ inline bool ua_f64_col(const AggSpec &agg, int col) {
+    return col >= 0 && ((agg.f64m >> col) & 1);
+}
 
 /* distinct-value multiset node (append-only pool) */
 struct Node {
@@ -194,6 +213,24 @@ __device__ inline void fold_f64(uint64_t *w, double dv) {
     } while (old != assumed);
 }
 
+/* The f64 add of the F64 kernels: the hardware global_atomic_add_f64 (no
+ * return value, no retry loop).  The state plane is hipMalloc'ed
+ * (coarse-grained) device memory, where the instruction is defined; under
+ * key skew the 64 lanes of a wave that hit one word queue at the memory
+ * side once instead of CAS-looping against each other
+ * (profiles/updagg_f64_note.md). */
+__device__ inline void add_f64(uint64_t *w, double dv) {
+    unsafeAtomicAdd((double *)w, dv);
+}
+
+/* an aggregate's argument as a double: the bits themselves when its column
+ * is flagged f64, the converted integer otherwise */
+__device__ inline double ua_arg(bool isf, int64_t v) {
+    double x;
+    memcpy(&x, &v, 8);
+    return isf ? x : (double)v;
+}
+
 /* ---- SQL NULL semantics (AmdUpdatingConfig.null_semantics == 1) ----
  *
  * Every aggregate keeps n_a, its count of live contributing rows (argument
@@ -226,8 +263,14 @@ __host__ __device__ inline int ua_width(int op, int null_semantics) {
  * consecutive rows of a wavefront share one word per column: blocks are 256
  * threads and the grid stride a multiple of 256, so a wave's first row is a
  * multiple of 64), skips the atomics of an aggregate whose argument is
- * null, and counts the contributing rows in the aggregate's n_a word. */
-template <bool NS>
+ * null, and counts the contributing rows in the aggregate's n_a word.
+ * F64 = true is the kernel of an operator with at least one f64 value
+ * column (AggSpec.f64m): SUM over such a column folds d * v as a double,
+ * MIN / MAX use the float encodings, the moment families convert each
+ * argument by its own column's flag, and every f64 fold is add_f64.  The
+ * chained aggregates pass raw bits either way.  F64 = false is the i64
+ * operator's code, untouched by the flags. */
+template <bool NS, bool F64>
 __device__ __forceinline__ void update_rows(const UpdateArgs &A,
                                             const uint64_t *const *valid) {
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -272,6 +315,63 @@ __device__ __forceinline__ void update_rows(const UpdateArgs &A,
                 if (ua_noff(op) != 0)
                     atomicAdd((unsigned long long *)&st[ua_noff(op)],
                               (unsigned long long)d);
+            }
+            if constexpr (F64) {
+                bool vf = ua_f64_col(A.agg, A.agg.col[a]);
+                bool done = true;
+                switch (A.agg.op[a]) {
+                case AMD_AGG_SUM:
+                    if (vf) add_f64(&st[0], (double)d * ua_arg(true, v));
+                    else done = false;
+                    break;
+                case AMD_AGG_AVG:
+                    atomicAdd((unsigned long long *)&st[0],
+                              (unsigned long long)d);
+                    add_f64(&st[1], (double)d * ua_arg(vf, v));
+                    break;
+                case AMD_AGG_MIN:
+                    if (d < 0) { *A.err = UERR_RETRACT; break; }
+                    atomicMax((unsigned long long *)&st[0],
+                              (unsigned long long)(vf ? enc_minf(v)
+                                                      : enc_min(v)));
+                    break;
+                case AMD_AGG_MAX:
+                    if (d < 0) { *A.err = UERR_RETRACT; break; }
+                    atomicMax((unsigned long long *)&st[0],
+                              (unsigned long long)(vf ? enc_maxf(v)
+                                                      : enc_max(v)));
+                    break;
+                case AMD_AGG_STDDEV:
+                case AMD_AGG_STDDEV_POP:
+                case AMD_AGG_VAR:
+                case AMD_AGG_VAR_POP: {
+                    double x = ua_arg(vf, v);
+                    add_f64(&st[0], (double)d * x);
+                    add_f64(&st[1], (double)d * x * x);
+                    break;
+                }
+                case AMD_AGG_COVAR_POP: case AMD_AGG_COVAR_SAMP:
+                case AMD_AGG_CORR: case AMD_AGG_REGR_SLOPE:
+                case AMD_AGG_REGR_INTERCEPT: case AMD_AGG_REGR_R2:
+                case AMD_AGG_REGR_AVGX: case AMD_AGG_REGR_AVGY:
+                case AMD_AGG_REGR_COUNT: case AMD_AGG_REGR_SXX:
+                case AMD_AGG_REGR_SYY: case AMD_AGG_REGR_SXY: {
+                    double y = ua_arg(vf, v);
+                    double x = ua_arg(
+                        ua_f64_col(A.agg, A.agg.col2[a]),
+                        A.cols[A.n_keys + A.agg.col2[a]][r]);
+                    add_f64(&st[0], d * y);
+                    add_f64(&st[1], d * x);
+                    add_f64(&st[2], d * x * y);
+                    add_f64(&st[3], d * y * y);
+                    add_f64(&st[4], d * x * x);
+                    break;
+                }
+                default:
+                    done = false;
+                    break;
+                }
+                if (done) continue;
             }
             switch (A.agg.op[a]) {
             case AMD_AGG_COUNT:
@@ -348,7 +448,12 @@ __device__ __forceinline__ void update_rows(const UpdateArgs &A,
 
 __global__ void __launch_bounds__(256)
 k_updagg_update(UpdateArgs A) {
-    update_rows<false>(A, nullptr);
+    update_rows<false, false>(A, nullptr);
+}
+
+__global__ void __launch_bounds__(256)
+k_updagg_update_f64(UpdateArgs A) {
+    update_rows<false, true>(A, nullptr);
 }
 
 struct UpdateArgsN {
@@ -358,7 +463,12 @@ struct UpdateArgsN {
 
 __global__ void __launch_bounds__(256)
 k_updagg_update_nullable(UpdateArgsN N) {
-    update_rows<true>(N.A, N.valid);
+    update_rows<true, false>(N.A, N.valid);
+}
+
+__global__ void __launch_bounds__(256)
+k_updagg_update_nullable_f64(UpdateArgsN N) {
+    update_rows<true, true>(N.A, N.valid);
 }
 
 /* evaluate one key's current values into out[n_aggs] (i64 / f64-bits).
@@ -367,8 +477,10 @@ k_updagg_update_nullable(UpdateArgsN N) {
 /* NS (null semantics): n_a replaces the key's row count wherever an
  * aggregate uses n, *vmask gets bit a set when aggregate a is non-NULL, and
  * the value under a NULL is 0.  NULL is decided from the condition (n_a == 0
- * or the result undefined), never by testing the result for NaN. */
-template <bool NS>
+ * or the result undefined), never by testing the result for NaN.
+ * F64: MIN / MAX over a flagged column decode with the float decoders; the
+ * f64 SUM word is emitted as it stands, which is the i64 SUM's code. */
+template <bool NS, bool F64>
 __device__ inline void ueval_slot(const UStore &S, const AggSpec &agg,
                                   int64_t slot, int64_t *out,
                                   unsigned *vmask) {
@@ -391,10 +503,14 @@ __device__ inline void ueval_slot(const UStore &S, const AggSpec &agg,
             break;
         case AMD_AGG_MIN:
             out[a] = dec_min(st[0]);
+            if constexpr (F64)
+                if (ua_f64_col(agg, agg.col[a])) out[a] = dec_minf(st[0]);
             if constexpr (NS) ok = na_rows > 0;
             break;
         case AMD_AGG_MAX:
             out[a] = dec_max(st[0]);
+            if constexpr (F64)
+                if (ua_f64_col(agg, agg.col[a])) out[a] = dec_maxf(st[0]);
             if constexpr (NS) ok = na_rows > 0;
             break;
         case AMD_AGG_AVG: {
@@ -655,6 +771,27 @@ __device__ __forceinline__ uint64_t ord_select(const volatile OrdEnt *ent,
     return prefix;
 }
 
+/* encoded word <-> raw value of a chained aggregate: enc_max order for an
+ * i64 column, the totalOrder float encoding for an f64 one */
+__device__ __forceinline__ uint64_t ord_enc(bool isf, int64_t v) {
+    return isf ? enc_maxf(v) : enc_max(v);
+}
+__device__ __forceinline__ int64_t ord_dec(bool isf, uint64_t e) {
+    return isf ? dec_maxf(e) : dec_max(e);
+}
+
+/* even-count median of an f64 column: (lo + hi) / 2.0, an IEEE add then an
+ * IEEE divide (DataFusion's); lo + hi may overflow to inf, NaN propagates */
+__device__ inline int64_t ord_midpoint_f64(int64_t lo, int64_t hi) {
+    double a, b;
+    memcpy(&a, &lo, 8);
+    memcpy(&b, &hi, 8);
+    double m = (a + b) / 2.0;
+    int64_t r;
+    memcpy(&r, &m, 8);
+    return r;
+}
+
 /* (lo + hi) / 2 truncated toward zero, without 64-bit overflow */
 __host__ __device__ inline int64_t ord_midpoint(int64_t lo, int64_t hi) {
     int64_t s = lo / 2 + hi / 2;
@@ -668,8 +805,11 @@ __host__ __device__ inline int64_t ord_midpoint(int64_t lo, int64_t hi) {
 
 /* NS: a (slot, aggregate) pair is selected when n_a > 0 (a key can have live
  * rows that are all NULL in the column: no select, no error) and the
- * multiset total is checked against n_a instead of the key's row count. */
-template <bool NS>
+ * multiset total is checked against n_a instead of the key's row count.
+ * F64: an aggregate over a flagged column gathers with the float encoding
+ * (the select and the shared-prefix skip work on encoded words and do not
+ * change); only the decode and the even-count midpoint differ. */
+template <bool NS, bool F64>
 __device__ __forceinline__ void ordstat_body(const OrdArgs &A,
                                              OrdEnt (*tile_all)[UORD_TILE],
                                              long long (*hist_all)[256]) {
@@ -681,9 +821,11 @@ __device__ __forceinline__ void ordstat_body(const OrdArgs &A,
     long long *hist = hist_all[wv];
     /* per-op bit masks over the aggregate index (no indexed reads of the
      * kernel-argument arrays by a lane-varying index) */
-    unsigned med = 0, mn = 0, mx = 0;
+    unsigned med = 0, mn = 0, mx = 0, fm = 0;
     for (int k = 0; k < AMD_MAX_AGGS; k++) {
         if (k >= na) break;
+        if constexpr (F64)
+            if (ua_f64_col(A.agg, A.agg.col[k])) fm |= 1u << k;
         if (A.agg.op[k] == AMD_AGG_MEDIAN) med |= 1u << k;
         if (A.agg.op[k] == AMD_AGG_MIN_RETRACT) mn |= 1u << k;
         if (A.agg.op[k] == AMD_AGG_MAX_RETRACT) mx |= 1u << k;
@@ -722,6 +864,7 @@ __device__ __forceinline__ void ordstat_body(const OrdArgs &A,
             todo &= todo - 1;
             int64_t slot = ws + (src >> 3);
             int a = src & 7;
+            bool isf = F64 && ((fm >> a) & 1);
             int32_t head = __shfl(lhead, src, 64);
             long long rows = __shfl(lrows, src, 64);
             /* gather: every lane walks the same chain (broadcast loads),
@@ -742,7 +885,7 @@ __device__ __forceinline__ void ordstat_body(const OrdArgs &A,
                 long long d = S.pool[j].delta;
                 j = S.pool[j].next;
                 if (d == 0) continue;          /* fully retracted value */
-                uint64_t e = enc_max(v);
+                uint64_t e = ord_enc(isf, v);
                 if (n < UORD_TILE && lane == 0) {
                     tile[n].enc = e;
                     tile[n].net = d;
@@ -777,7 +920,7 @@ __device__ __forceinline__ void ordstat_body(const OrdArgs &A,
                         j = S.pool[j].next;
                         if (d == 0) continue;
                         if (lane == 0) {
-                            dst[i].enc = enc_max(v);
+                            dst[i].enc = ord_enc(isf, v);
                             dst[i].net = d;
                         }
                         i++;
@@ -802,20 +945,22 @@ __device__ __forceinline__ void ordstat_body(const OrdArgs &A,
                 uint64_t pre =
                     ptop == 7 ? 0ULL : first & (~0ULL << ((ptop + 1) * 8));
                 if ((mn >> a) & 1) {
-                    res = dec_max(
-                        ord_select(ent, n, 0, pre, ptop, hist, lane, &sbad));
+                    res = ord_dec(isf, ord_select(ent, n, 0, pre, ptop, hist,
+                                                  lane, &sbad));
                 } else if ((mx >> a) & 1) {
-                    res = dec_max(ord_select(ent, n, W - 1, pre, ptop, hist,
-                                             lane, &sbad));
+                    res = ord_dec(isf, ord_select(ent, n, W - 1, pre, ptop,
+                                                  hist, lane, &sbad));
                 } else {
-                    int64_t hi = dec_max(ord_select(ent, n, W / 2, pre, ptop,
-                                                    hist, lane, &sbad));
+                    int64_t hi =
+                        ord_dec(isf, ord_select(ent, n, W / 2, pre, ptop,
+                                                hist, lane, &sbad));
                     res = hi;
                     if (!(W & 1)) {
                         int64_t lo =
-                            dec_max(ord_select(ent, n, (W - 1) / 2, pre,
-                                               ptop, hist, lane, &sbad));
-                        res = ord_midpoint(lo, hi);
+                            ord_dec(isf, ord_select(ent, n, (W - 1) / 2, pre,
+                                                    ptop, hist, lane, &sbad));
+                        res = isf ? ord_midpoint_f64(lo, hi)
+                                  : ord_midpoint(lo, hi);
                     }
                 }
                 if (sbad && lane == 0) *A.err = UERR_ORD_ROWS;
@@ -830,14 +975,54 @@ __global__ void __launch_bounds__(64 * UORD_WAVES)
 k_updagg_ordstat(OrdArgs A) {
     __shared__ OrdEnt tile_all[UORD_WAVES][UORD_TILE];
     __shared__ long long hist_all[UORD_WAVES][256];
-    ordstat_body<false>(A, tile_all, hist_all);
+    ordstat_body<false, false>(A, tile_all, hist_all);
+}
+
+__global__ void __launch_bounds__(64 * UORD_WAVES)
+k_updagg_ordstat_f64(OrdArgs A) {
+    __shared__ OrdEnt tile_all[UORD_WAVES][UORD_TILE];
+    __shared__ long long hist_all[UORD_WAVES][256];
+    ordstat_body<false, true>(A, tile_all, hist_all);
 }
 
 __global__ void __launch_bounds__(64 * UORD_WAVES)
 k_updagg_ordstat_nullable(OrdArgs A) {
     __shared__ OrdEnt tile_all[UORD_WAVES][UORD_TILE];
     __shared__ long long hist_all[UORD_WAVES][256];
-    ordstat_body<true>(A, tile_all, hist_all);
+    ordstat_body<true, false>(A, tile_all, hist_all);
+}
+
+__global__ void __launch_bounds__(64 * UORD_WAVES)
+k_updagg_ordstat_nullable_f64(OrdArgs A) {
+    __shared__ OrdEnt tile_all[UORD_WAVES][UORD_TILE];
+    __shared__ long long hist_all[UORD_WAVES][256];
+    ordstat_body<true, true>(A, tile_all, hist_all);
+}
+
+/* f64 subtraction is not exact: a key whose rows were all retracted (1e16,
+ * 1.0, -1e16, -1.0 leaves -1.0) would hand the residue to its next life.
+ * The reference drops the key's accumulators at the flush that finds it
+ * empty (incremental_aggregator.rs:671-686); here that flush puts the sum
+ * words fed by an f64 column back to +0.0.  The counts (n_a, AVG's count)
+ * are integers and already 0.  k_updagg_expire clears the whole state. */
+__device__ inline void ua_reset_f64(const UStore &S, const AggSpec &agg,
+                                    int64_t slot) {
+    uint64_t *stp = S.st + (size_t)slot * agg.SW;
+    for (int a = 0; a < agg.n_aggs; a++) {
+        uint64_t *st = stp + agg.soff[a];
+        int op = agg.op[a];
+        bool vf = ua_f64_col(agg, agg.col[a]);
+        if (op == AMD_AGG_SUM && vf) {
+            st[0] = 0;
+        } else if (op == AMD_AGG_AVG && vf) {
+            st[1] = 0;
+        } else if (op >= AMD_AGG_STDDEV && op <= AMD_AGG_VAR_POP && vf) {
+            st[0] = st[1] = 0;
+        } else if (ua_is_comoment(op) &&
+                   (vf || ua_f64_col(agg, agg.col2[a]))) {
+            for (int k = 0; k < 5; k++) st[k] = 0;
+        }
+    }
 }
 
 struct FlushArgs {
@@ -858,8 +1043,10 @@ struct FlushArgs {
  * equals NULL and differs from every value (the value plane under a NULL is
  * 0, so mask equality plus value equality is exactly that) -- and every
  * emitted row carries its validity mask: bit a set = aggregate a non-NULL.
- * Retract rows re-emit the mask that was emitted with the row they retract. */
-template <bool NS>
+ * Retract rows re-emit the mask that was emitted with the row they retract.
+ * F64: a touched key with zero live rows gets its f64-fed sum words reset
+ * (ua_reset_f64); the unchanged-value test stays a bit compare. */
+template <bool NS, bool F64>
 __device__ __forceinline__ void flush_body(const FlushArgs &F) {
     const UStore &S = F.store;
     int na = F.agg.n_aggs;
@@ -880,7 +1067,9 @@ __device__ __forceinline__ void flush_body(const FlushArgs &F) {
             (slot == (int64_t)S.C ? true : S.keys[slot] != EMPTY_KEY)) {
             key = slot == (int64_t)S.C ? EMPTY_KEY : S.keys[slot];
             long long rows = S.rows[slot];
-            if (rows > 0) ueval_slot<NS>(S, F.agg, slot, cur, &curv);
+            if (rows > 0) ueval_slot<NS, F64>(S, F.agg, slot, cur, &curv);
+            if constexpr (F64)
+                if (rows == 0) ua_reset_f64(S, F.agg, slot);
             if (S.emitted[slot]) {
                 bool same = rows > 0;
                 if constexpr (NS) same = same && curv == F.lastv[slot];
@@ -948,12 +1137,22 @@ __device__ __forceinline__ void flush_body(const FlushArgs &F) {
 
 __global__ void __launch_bounds__(256)
 k_updagg_flush(FlushArgs F) {
-    flush_body<false>(F);
+    flush_body<false, false>(F);
+}
+
+__global__ void __launch_bounds__(256)
+k_updagg_flush_f64(FlushArgs F) {
+    flush_body<false, true>(F);
 }
 
 __global__ void __launch_bounds__(256)
 k_updagg_flush_nullable(FlushArgs F) {
-    flush_body<true>(F);
+    flush_body<true, false>(F);
+}
+
+__global__ void __launch_bounds__(256)
+k_updagg_flush_nullable_f64(FlushArgs F) {
+    flush_body<true, true>(F);
 }
 
 /* Per-row validity masks -> per-aggregate Arrow validity bitmaps.  One
@@ -1164,6 +1363,7 @@ struct GpuUpdAgg : OpBase {
     int has_ord;                /* config has MEDIAN / MIN_RETRACT / MAX_RETRACT */
     OrdEnt *d_arena;            /* [pool_cap] wide-chain scratch (has_ord) */
     unsigned long long *d_arena_cur;
+    int f64;                    /* some value column is f64: the *_f64 kernels */
     /* null semantics (cfg.null_semantics == 1) only */
     int ns;
     uint32_t *d_lastv;          /* [C+1] last-emitted validity mask */
@@ -1211,10 +1411,40 @@ API void *arroyo_amd_updagg_create(const AmdUpdatingConfig *cfg) {
                  cfg->null_semantics);
         return nullptr;
     }
+    uint32_t f64m = 0;
+    for (int c = 0; c < 8; c++) {
+        int f = cfg->val_is_f64[c];
+        if (f != 0 && f != 1) {
+            snprintf(g_create_err, sizeof g_create_err,
+                     "invalid updagg config: val_is_f64[%d] = %d (0 or 1)",
+                     c, f);
+            return nullptr;
+        }
+        if (f && c >= cfg->n_value_cols) {
+            snprintf(g_create_err, sizeof g_create_err,
+                     "invalid updagg config: val_is_f64[%d] set, but there "
+                     "are %d value columns", c, cfg->n_value_cols);
+            return nullptr;
+        }
+        if (f) f64m |= 1u << c;
+    }
+    for (int i = 0; i < cfg->n_aggs; i++) {
+        int op = cfg->agg_ops[i], col = cfg->agg_col[i];
+        if ((op == AMD_AGG_BIT_AND || op == AMD_AGG_BIT_OR ||
+             op == AMD_AGG_BIT_XOR) &&
+            col >= 0 && col < 8 && ((f64m >> col) & 1)) {
+            snprintf(g_create_err, sizeof g_create_err,
+                     "invalid updagg config: bitwise aggregate op %d over "
+                     "f64 value column %d", op, col);
+            return nullptr;
+        }
+    }
     GpuUpdAgg *o = new GpuUpdAgg();
     o->cfg = *cfg;
     o->has_ord = has_ord;
     o->ns = cfg->null_semantics;
+    o->f64 = f64m != 0;
+    o->agg.f64m = f64m;
     o->agg.n_aggs = cfg->n_aggs;
     o->agg.SW = 0;
     for (int i = 0; i < cfg->n_aggs; i++) {
@@ -1326,6 +1556,23 @@ static void ua_fill_update_args(GpuUpdAgg *o, UpdateArgs *A, int64_t n_rows) {
     A->err = o->d_err;
 }
 
+/* the update kernel of this operator's (null_semantics, f64) pair */
+static void ua_launch_update(GpuUpdAgg *o, const UpdateArgsN &N,
+                             int64_t n_rows) {
+    dim3 grid(grid_for(n_rows, 2048)), block(256);
+    if (o->ns && o->f64)
+        hipLaunchKernelGGL(k_updagg_update_nullable_f64, grid, block, 0,
+                           o->stream, N);
+    else if (o->ns)
+        hipLaunchKernelGGL(k_updagg_update_nullable, grid, block, 0,
+                           o->stream, N);
+    else if (o->f64)
+        hipLaunchKernelGGL(k_updagg_update_f64, grid, block, 0, o->stream,
+                           N.A);
+    else
+        hipLaunchKernelGGL(k_updagg_update, grid, block, 0, o->stream, N.A);
+}
+
 /* shared argument checks of the nullable entry points */
 static int ua_check_nullable(GpuUpdAgg *o, const uint8_t *const *validity,
                              int32_t n_cols) {
@@ -1378,13 +1625,7 @@ static int ua_process_host(GpuUpdAgg *o, const int64_t *const *cols,
             N.valid[v] = (const uint64_t *)o->stg_v.d[v];
         }
         ua_fill_update_args(o, &A, take);
-        if (o->ns)
-            hipLaunchKernelGGL(k_updagg_update_nullable,
-                               dim3(grid_for(take, 2048)),
-                               dim3(256), 0, o->stream, N);
-        else
-            hipLaunchKernelGGL(k_updagg_update, dim3(grid_for(take, 2048)),
-                               dim3(256), 0, o->stream, A);
+        ua_launch_update(o, N, take);
         HIP_CHECK(o, hipGetLastError());
         HIP_CHECK(o, hipStreamSynchronize(o->stream));
         done += take;
@@ -1409,14 +1650,7 @@ static int ua_process_device(GpuUpdAgg *o, const int64_t *const *dcols,
         N.valid[v] = (const uint64_t *)bm;
     }
     ua_fill_update_args(o, &A, n_rows);
-    if (o->ns)
-        hipLaunchKernelGGL(k_updagg_update_nullable,
-                           dim3(grid_for(n_rows, 2048)),
-                           dim3(256), 0, o->stream, N);
-    else
-        hipLaunchKernelGGL(k_updagg_update, dim3(grid_for(n_rows, 2048)),
-                           dim3(256),
-                           0, o->stream, A);
+    ua_launch_update(o, N, n_rows);
     HIP_CHECK(o, hipGetLastError());
     return 0;
 }
@@ -1502,6 +1736,18 @@ static int ua_fill_validity(GpuUpdAgg *o, AmdOutBatch *out) {
 /* the emitted rows and their bitmaps into the allocated batch; an error
  * leaves `out` freed and zeroed */
 static int ua_out_rows(GpuUpdAgg *o, AmdOutBatch *out, int64_t n) {
+    /* f64 outputs, on flush and expire alike: AVG and the moment families
+     * always, and the aggregates that hand an f64 argument through */
+    for (int a = 0; a < o->cfg.n_aggs; a++) {
+        int op = o->cfg.agg_ops[a];
+        if (op == AMD_AGG_AVG ||
+            (op >= AMD_AGG_STDDEV && op <= AMD_AGG_VAR_POP) ||
+            (ua_is_comoment(op) && op != AMD_AGG_REGR_COUNT) ||
+            ((op == AMD_AGG_SUM || op == AMD_AGG_MIN || op == AMD_AGG_MAX ||
+              ua_is_ord(op)) &&
+             ua_f64_col(o->agg, o->cfg.agg_col[a])))
+            out->is_f64[o->cfg.n_keys + a] = 1;
+    }
     if (out_copy_cols(o, out, o->d_out, n)) return 1;
     if (!ua_fill_validity(o, out)) return 0;
     out_free_host(out);
@@ -1524,14 +1770,11 @@ API int arroyo_amd_updagg_flush(void *h, AmdOutBatch *out) {
         R.arena_cap = o->store.pool_cap;
         R.err = o->d_err;
         int64_t waves = ((int64_t)o->store.C + 1 + 7) / 8;
-        if (o->ns)
-            hipLaunchKernelGGL(k_updagg_ordstat_nullable,
-                               dim3(grid_for(waves * 64, 2048)),
-                               dim3(64 * UORD_WAVES), 0, o->stream, R);
-        else
-            hipLaunchKernelGGL(k_updagg_ordstat,
-                               dim3(grid_for(waves * 64, 2048)),
-                               dim3(64 * UORD_WAVES), 0, o->stream, R);
+        auto ordk = o->ns ? (o->f64 ? k_updagg_ordstat_nullable_f64
+                                    : k_updagg_ordstat_nullable)
+                          : (o->f64 ? k_updagg_ordstat_f64 : k_updagg_ordstat);
+        hipLaunchKernelGGL(ordk, dim3(grid_for(waves * 64, 2048)),
+                           dim3(64 * UORD_WAVES), 0, o->stream, R);
         HIP_CHECK(o, hipGetLastError());
     }
     FlushArgs F = {};
@@ -1545,16 +1788,11 @@ API int arroyo_amd_updagg_flush(void *h, AmdOutBatch *out) {
     F.err = o->d_err;
     F.lastv = o->d_lastv;
     F.vmask = o->d_vmask;
-    if (o->ns)
-        hipLaunchKernelGGL(k_updagg_flush_nullable,
-                           dim3(grid_for((int64_t)o->store.C + 1, 2048)),
-                           dim3(256),
-                           0, o->stream, F);
-    else
-        hipLaunchKernelGGL(k_updagg_flush,
-                           dim3(grid_for((int64_t)o->store.C + 1, 2048)),
-                           dim3(256),
-                           0, o->stream, F);
+    auto flushk = o->ns ? (o->f64 ? k_updagg_flush_nullable_f64
+                                  : k_updagg_flush_nullable)
+                        : (o->f64 ? k_updagg_flush_f64 : k_updagg_flush);
+    hipLaunchKernelGGL(flushk, dim3(grid_for((int64_t)o->store.C + 1, 2048)),
+                       dim3(256), 0, o->stream, F);
     HIP_CHECK(o, hipGetLastError());
     unsigned long long n = 0;
     HIP_CHECK(o, hipMemcpyAsync(&n, o->d_n_out, 8, hipMemcpyDeviceToHost,
@@ -1565,14 +1803,6 @@ API int arroyo_amd_updagg_flush(void *h, AmdOutBatch *out) {
     if (out) {
         if (op_out_alloc(o, out, (int64_t)n, o->out_cols, __func__))
             return 1;
-        for (int a = 0; a < o->cfg.n_aggs; a++)
-            if (o->cfg.agg_ops[a] == AMD_AGG_AVG ||
-                (o->cfg.agg_ops[a] >= AMD_AGG_STDDEV &&
-                 o->cfg.agg_ops[a] <= AMD_AGG_VAR_POP) ||
-                (o->cfg.agg_ops[a] >= AMD_AGG_COVAR_POP &&
-                 o->cfg.agg_ops[a] <= AMD_AGG_REGR_SXY &&
-                 o->cfg.agg_ops[a] != AMD_AGG_REGR_COUNT))
-                out->is_f64[o->cfg.n_keys + a] = 1;
         if (ua_out_rows(o, out, (int64_t)n)) return 1;
     }
     return 0;

@@ -273,7 +273,9 @@ const char *arroyo_amd_expjoin_last_error(void *h);
  *                            keyed_aggregate/global_aggregate (:778-884);
  *                            cols [key?, vals..., is_retract] where
  *                            is_retract mirrors _updating_meta.is_retract
- *                            (get_retracts :740-758)
+ *                            (get_retracts :740-758); a value column
+ *                            flagged in cfg.val_is_f64 holds f64 bit
+ *                            patterns, on every ingest surface
  *   updagg_flush         <-> handle_tick/on_close -> flush (:637-737):
  *                            out columns [key?, agg outputs...,
  *                            is_retract]

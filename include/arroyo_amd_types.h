@@ -239,7 +239,44 @@ typedef struct {
  * over an updating input.  Their cost is linear in the distinct values a
  * key has ever held (log2_nodes bounds the pool; zero-net nodes are not
  * reclaimed).  Unknown op codes are rejected at create.  Flush cadence is
- * driven by the caller (the reference's tick timer). */
+ * driven by the caller (the reference's tick timer).
+ *
+ * Float64 value columns (val_is_f64[c] = 1): column c travels as f64 bit
+ * patterns in its i64 plane, on the host surface and on the *_device ones,
+ * with and without null_semantics; a Float32 SQL column is widened to f64
+ * by the caller.  The rules below are restated from DataFusion 48 and
+ * arrow-arith, whose sources are not in the reference tree: restated, not
+ * golden-pinned (the checker is the Python model tests/updagg_f64_ref.py;
+ * the C oracle does not read the field).  For an aggregate whose argument
+ * column is flagged: SUM keeps one f64 word starting at +0.0 (an append
+ * adds v, a retraction adds -v) and AVG keeps (count, f64 sum); MIN / MAX /
+ * MIN_RETRACT / MAX_RETRACT / MEDIAN order the values by IEEE totalOrder on
+ * the bit patterns (-NaN < -inf < ... < -0.0 < +0.0 < ... < +inf < +NaN)
+ * and return a stored value bit for bit, MEDIAN of an even count being
+ * (lo + hi) / 2.0 as two IEEE binary64 operations (it may overflow to inf;
+ * NaN propagates); the outputs of these are f64 and AmdOutBatch.is_f64 is
+ * set.  The moment and co-moment families convert each argument by its own
+ * column's flag (reinterpret when flagged, (double)v otherwise), so one
+ * f64 and one i64 argument is legal; REGR_COUNT stays i64.  In an operator
+ * with a flagged column every f64 sum word, those of AVG and the moments
+ * over its i64 columns included, folds with the hardware f64 atomic add
+ * (an operator without a flag keeps the compare-and-swap fold); both are
+ * one IEEE add per row in arrival order.  flush and expire mark the same
+ * output columns in AmdOutBatch.is_f64.  COUNT(col) is
+ * unchanged.  COUNT DISTINCT is unchanged too: identity is by raw bits, so
+ * -0.0 and +0.0 are two values and NaN payloads are distinct.  BIT_AND /
+ * BIT_OR / BIT_XOR over a flagged column, a flag on a column index >=
+ * n_value_cols and a flag value other than 0 / 1 are rejected at create.
+ * f64 subtraction is not exact, so a key whose rows have all been retracted
+ * could keep a residue in its sum words: the flush that finds a touched key
+ * with zero live rows resets the sum words fed by a flagged column to +0.0
+ * (the reference drops the key's accumulators there,
+ * incremental_aggregator.rs:671-686), and expire clears the whole state.
+ * Drain / restore carry state words raw: restoring into an operator with
+ * different flags is the caller's error, as for every other config field.
+ * val_is_f64 sits before null_semantics, which stays the struct's last
+ * field: a caller compiled against the struct without val_is_f64 must be
+ * rebuilt (its null_semantics would be read as val_is_f64[0]). */
 typedef struct {
     int32_t  n_keys;            /* 0 or 1 */
     int32_t  n_value_cols;
@@ -253,6 +290,9 @@ typedef struct {
     uint32_t log2_out_cap;
     int32_t  device;
     int32_t  emit_to_host;
+    int32_t  val_is_f64[8];     /* per value column: 1 = the i64 plane holds
+                                   f64 bit patterns (see above); all zeros is
+                                   the i64 operator, bit for bit */
     int32_t  null_semantics;    /* 0: non-nullable value columns, NaN where
                                    the reference emits SQL NULL, no output
                                    validity (the contract above, unchanged).
